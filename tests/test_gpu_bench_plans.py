@@ -14,7 +14,7 @@ weights, captured hipGraph with lanes -- and compared, per pair, with
 
 Every conv launch of a plan reports the instantiation it takes (fn2_conv2d_kernel_name); the tests print the set, and
 test_every_instantiation_of_the_timed_plans_is_compared asserts that the plans checked here cover every instantiation
-bench.py's default run and its --mode train run launch.
+bench.py --full and its --mode train run launch.
 """
 import os
 
@@ -206,7 +206,7 @@ def test_timed_train_step_equals_eager_and_moves_the_weights():
 
 
 def test_every_instantiation_of_the_timed_plans_is_compared():
-    """What bench.py launches by default (FlowNet2 b4, then FlowNetC b8 and FlowNetS b8 under `extra`), with
+    """What bench.py --full launches (FlowNet2 b4, then FlowNetC b8 and FlowNetS b8 under `extra`), with
     --height 448 --width 1024 and with --mode train is exactly what the tests above compared: rebuild the engines the
     way bench.py does and require every conv / filter-gradient instantiation to be in the compared set."""
     from src import weights as W

@@ -321,3 +321,26 @@ def test_oracle_fusion_transposed_convs_read_their_biases():
     np.testing.assert_allclose(sc.deconv(x, "d", act=False), plain, atol=1e-12)  # biases_initializer=None scope: not read
     with pytest.raises(KeyError):
         refm._Scope({"S/d/weights": w}, "S").deconv(x, "d", bias=True)
+
+
+def test_bench_dump_outputs_dtypes_cap_and_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 (float64 kept), '/' in a name becomes '_', and past the byte cap every array is
+    cut to a seeded sample of its entries that is the same from run to run."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.dump_outputs(str(tmp_path / "a"), {"F2/flow": torch.ones(2, 3, dtype=torch.float16), "loss": np.array([0.5])})
+    f, l = np.load(tmp_path / "a" / "F2_flow.npy"), np.load(tmp_path / "a" / "loss.npy")
+    assert f.dtype == np.float32 and f.shape == (2, 3) and l.dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    big = {"x": torch.arange(3000, dtype=torch.float32), "y": np.arange(1000.0)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    sizes = 0
+    for name in ("x", "y"):
+        b, c = np.load(tmp_path / "b" / (name + ".npy")), np.load(tmp_path / "c" / (name + ".npy"))
+        assert np.array_equal(b, c) and np.all(np.diff(b) > 0)
+        sizes += b.nbytes
+    assert 0 < sizes <= 4000

@@ -4,7 +4,7 @@ modes=$1; shift
 for rep in 1 2; do
   for dbg in $modes; do
     export FN2_CONV_DBG=$dbg
-    python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys,os; d=json.loads(sys.stdin.read()); print('dbg', os.environ['FN2_CONV_DBG'], d['ms_per_step'], d['value'])"
   done
 done

@@ -5,7 +5,7 @@ var=$1; vals=$2; shift 2
 for rep in 1 2; do
   for v in $vals; do
     export $var=$v
-    python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys,os; d=json.loads(sys.stdin.read()); print('$var', os.environ['$var'], d['ms_per_step'], d['value'])"
   done
 done

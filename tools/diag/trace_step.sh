@@ -3,7 +3,7 @@ root=$(pwd)
 out=$root/gpurun_out/trace_r3
 rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d $out/t --output-format csv -- python $root/bench.py --no-extra --no-cpu-baseline --regions 1 --steps 10 > $out/bench.json 2> $out/err.txt
+rocprofv3 --kernel-trace -d $out/t --output-format csv -- python $root/bench.py --full --no-extra --no-cpu-baseline --regions 1 --steps 10 > $out/bench.json 2> $out/err.txt
 f=$(ls $out/t/*/*kernel_trace.csv | head -1)
 head -1 $f > $out/header.txt
 python $root/tools/graph_timeline.py $f -3 -v > $out/timeline.txt

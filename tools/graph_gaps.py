@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Idle time inside captured forward steps, from a rocprofv3 --kernel-trace CSV:
-    rocprofv3 --kernel-trace -d out --output-format csv -- python3 bench.py --no-extra --no-cpu-baseline --regions 1
+    rocprofv3 --kernel-trace -d out --output-format csv -- python3 bench.py --full --no-extra --no-cpu-baseline --regions 1
     python tools/graph_gaps.py out/*/*kernel_trace.csv
 Splits the trace at the first kernel of a step (the name that opens the graph), then reports per step: wall (first
 start .. last end), the union of the kernel intervals (time with at least one kernel running), the idle remainder and

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 stats() {  # name, bench args...
   local name=$1; shift
   rm -rf $out/tmp_$name
-  rocprofv3 --kernel-trace --stats -d $out/tmp_$name --output-format csv -- python $root/bench.py "$@" --no-cpu-baseline \
+  rocprofv3 --kernel-trace --stats -d $out/tmp_$name --output-format csv -- python $root/bench.py --full "$@" --no-cpu-baseline \
       > $out/${tag}_${name}_bench_under_rocprof.json 2> $out/tmp_$name.err
   cp $(ls $out/tmp_$name/*/*kernel_stats.csv | head -1) $out/${tag}_${name}_kernel_stats.csv
   rm -rf $out/tmp_$name
@@ -30,7 +30,7 @@ stats flownets_train_b8_f16x2 --mode train --steps 10 --warmup 3
 pmc() {  # name, counter, bench args...
   local name=$1 counter=$2; shift 2
   rm -rf $out/pmc_${name}_$counter
-  rocprofv3 --kernel-trace --pmc $counter -d $out/pmc_${name}_$counter --output-format csv -- python $root/bench.py "$@" \
+  rocprofv3 --kernel-trace --pmc $counter -d $out/pmc_${name}_$counter --output-format csv -- python $root/bench.py --full "$@" \
       --no-cpu-baseline --no-graph --steps 3 --warmup 1 > /dev/null 2> $out/pmc_${name}_$counter.err
 }
 export FN2_TRAIN_GRAPH=0   # (counter passes name kernels per launch: the eager train step)
@@ -49,12 +49,12 @@ unset FN2_TRAIN_GRAPH
 python $root/tools/bench_ops.py > $out/${tag}_ops_bandwidth_b8.json 2> /dev/null
 python $root/tools/bench_ops.py --batch 64 > $out/${tag}_ops_bandwidth_b64.json 2> /dev/null
 # the plain (un-profiled) headline run: the driver's command line, CPU baseline and the FlowNetC extra included
-python $root/bench.py > $out/${tag}_default_flownet2_b4_f16x2_bench.json 2> /dev/null
-python $root/bench.py --height 436 --width 1024 --steps 10 --warmup 3 --no-cpu-baseline \
+python $root/bench.py --full > $out/${tag}_default_flownet2_b4_f16x2_bench.json 2> /dev/null
+python $root/bench.py --full --height 436 --width 1024 --steps 10 --warmup 3 --no-cpu-baseline \
     > $out/${tag}_flownet2_b4_1024x436_f16x2_bench.json 2> /dev/null
-python $root/bench.py --model FlowNetC --batch 8 --no-extra --no-cpu-baseline > $out/${tag}_flownetc_b8_f16x2_bench.json 2> /dev/null
-python $root/bench.py --model FlowNetS --batch 8 --no-extra --no-cpu-baseline > $out/${tag}_flownets_b8_f16x2_bench.json 2> /dev/null
-FN2_DIST_SINGLE=1 python $root/bench.py --no-cpu-baseline > $out/${tag}_default_rccl_single_rank_rehearsal.json 2> /dev/null
-python $root/bench.py --gpus 2 --no-cpu-baseline > $out/${tag}_default_gpus2_gloo_rehearsal.json 2> /dev/null
-python $root/bench.py --mode train --steps 10 --warmup 3 > $out/${tag}_flownets_train_b8_f16x2_bench.json 2> /dev/null
+python $root/bench.py --full --model FlowNetC --batch 8 --no-extra --no-cpu-baseline > $out/${tag}_flownetc_b8_f16x2_bench.json 2> /dev/null
+python $root/bench.py --full --model FlowNetS --batch 8 --no-extra --no-cpu-baseline > $out/${tag}_flownets_b8_f16x2_bench.json 2> /dev/null
+FN2_DIST_SINGLE=1 python $root/bench.py --full --no-cpu-baseline > $out/${tag}_default_rccl_single_rank_rehearsal.json 2> /dev/null
+python $root/bench.py --full --gpus 2 --no-cpu-baseline > $out/${tag}_default_gpus2_gloo_rehearsal.json 2> /dev/null
+python $root/bench.py --full --mode train --steps 10 --warmup 3 > $out/${tag}_flownets_train_b8_f16x2_bench.json 2> /dev/null
 ls -la $out
