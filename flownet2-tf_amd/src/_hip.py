@@ -104,6 +104,9 @@ PROTOTYPES = {
     "fn2_head_g18": (_i, [_p, _tp, _p]),
     "fn2_head_bwd_data": (_i, [_p, _p, _tp, _i, _i, _p]),
     "fn2_conv2d_bwd_filter": (_i, [C.POINTER(Fn2BwdwDesc), _p]),
+    "fn2_variational_workspace_bytes": (C.c_int64, [_i, _i, _i]),
+    "fn2_variational_refine": (_i, [_p, _p, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int64, _i, _i, _i, _f, _f, _f, _f,
+                                    _i, _i, _i, _f, _p, C.c_int64, _p]),
     "fn2_capture_begin": (_i, [_p]),
     "fn2_capture_end": (_i, [_p, C.POINTER(C.c_void_p)]),
     "fn2_graph_launch": (_i, [_p, _p]),

@@ -1,6 +1,7 @@
 """python -m src.flownet_s_interp.test --input_a I1 --matches_a MASK --sparse_flow SF.flo --out DIR
 (flags of /root/reference src/flownet_s_interp/test.py:60-190 that apply to single-frame inference; a .txt
---input_a runs Net.test_batch on image pairs).  --checkpoint (.npz) and --dtype are this build's extras."""
+--input_a runs Net.test_batch on image pairs).  --checkpoint (.npz) and --dtype are this build's extras;
+--variational_refinement (:207-214) refines the flow between --input_a and --input_b."""
 import argparse
 import os
 
@@ -37,10 +38,11 @@ def main():
         save_image=FLAGS.save_image,
         compute_metrics=FLAGS.compute_metrics,
         new_par_folder=FLAGS.new_par_folder,
+        variational_refinement=FLAGS.variational_refinement,
     )
 
 
-if __name__ == '__main__':
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--input_a', type=str, required=True, help='Path to first image')
     parser.add_argument('--input_b', type=str, default=None, help='Path to second image (unused by the network)')
@@ -55,7 +57,14 @@ if __name__ == '__main__':
     parser.add_argument('--compute_metrics', type=str2bool, nargs='?', default=True)
     parser.add_argument('--new_par_folder', type=str, default=None)
     parser.add_argument('--dtype', type=str, default='f32', choices=['f32', 'bf16', 'f16', 'f16x2'])
-    FLAGS = parser.parse_args()
+    parser.add_argument('--variational_refinement', type=str2bool, nargs='?', default=False,
+                        help='Refine the output flow with the EpicFlow variational energy minimisation (on the GPU; '
+                             'needs --input_b)')
+    return parser
+
+
+if __name__ == '__main__':
+    FLAGS = build_parser().parse_args()
     for flag in ('input_a', 'matches_a', 'sparse_flow'):
         if not os.path.exists(getattr(FLAGS, flag)):
             raise ValueError('%s path must exist' % flag)

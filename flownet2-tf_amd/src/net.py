@@ -191,8 +191,11 @@ class Net(object):
     # ---- single-pair inference ----------------------------------------------------------------------
     def test(self, checkpoint, input_a_path, input_b_path=None, matches_a_path=None, sparse_flow_path=None,
              out_path='./', input_type='image_pairs', save_image=True, save_flo=True, compute_metrics=True,
-             gt_flow=None, new_par_folder=None):
-        """net.py:484-628.  input_type 'image_matches' (FlowNetS_interp): first image + match mask + sparse flow."""
+             gt_flow=None, new_par_folder=None, variational_refinement=False):
+        """net.py:484-628.  input_type 'image_matches' (FlowNetS_interp): first image + match mask + sparse flow.
+        `variational_refinement` (with `input_b_path`): the cropped flow is refined on the device by the EpicFlow
+        energy minimisation (src/variational.py, the reference's defaults) before metrics and outputs, as
+        net.py:578-589 does through its external binary."""
         if self.weights is None:
             self.load_weights(checkpoint)
         if input_type == 'image_matches':
@@ -205,9 +208,17 @@ class Net(object):
             # image files decode to uint8: they cross the host link as bytes and are normalised on the device
             a, b, info, scale = self.adapt_x_u8(imread(input_a_path), imread(input_b_path))
             preds = self.model({'input_a': a, 'input_b': b, 'scale': scale}, LONG_SCHEDULE, trainable=False)
-        flow = preds['flow'][0].float().cpu().numpy()
         y_info = (info[-3], info[-2], 2) if info is not None else None
-        flow = self.postproc_y_hat_test(flow, y_info)
+        if variational_refinement and input_b_path is not None:
+            from .variational import refine
+            pred = self.postproc_y_hat_test(preds['flow'][0].float(), y_info)
+            dev = pred.device
+            fa = torch.from_numpy(np.ascontiguousarray(imread(input_a_path))).to(dev)
+            fb = torch.from_numpy(np.ascontiguousarray(imread(input_b_path))).to(dev)
+            flow = refine(pred, fa, fb).cpu().numpy()
+        else:
+            flow = preds['flow'][0].float().cpu().numpy()
+            flow = self.postproc_y_hat_test(flow, y_info)
 
         parent = new_par_folder if new_par_folder is not None else \
             os.path.basename(os.path.dirname(os.path.abspath(input_a_path)))
@@ -244,11 +255,11 @@ class Net(object):
         `accumulate_metrics` appends the sequence averages.  `width`/`height` are kept for signature
         compatibility (the reference sizes its placeholders with them); frames are padded by their own size.
         `batch_size` pairs of equal size go through the engine per launch (the reference feeds one pair per
-        sess.run).  The 'image_matches' input type belongs to FlowNetS_interp and is not built."""
+        sess.run).  `variational_refinement` refines the cropped flows of each group of equally sized frames in one
+        device call (src/variational.py; the reference runs its binary per pair, net.py:889-901).  The
+        'image_matches' input type belongs to FlowNetS_interp and is not built."""
         if input_type != 'image_pairs':
             raise NotImplementedError("test_batch: only input_type='image_pairs' (FlowNetS_interp is out of scope)")
-        if variational_refinement:
-            raise NotImplementedError("test_batch: variational refinement calls an external binary (out of scope)")
         if self.weights is None:
             self.load_weights(checkpoint)
         with open(image_paths, 'r') as f:
@@ -268,7 +279,7 @@ class Net(object):
         try:
             for start in range(0, len(lines), batch_size):
                 chunk = lines[start:start + batch_size]
-                for paths, flow in zip(chunk, self._infer_pairs(chunk, batch_size)):
+                for paths, flow in zip(chunk, self._infer_pairs(chunk, batch_size, variational_refinement)):
                     flows.append(flow)
                     assert 2 <= len(paths) <= 5, 'expected: img1 img2 [gt_flow [occ_mask [inv_mask]]]'
                     gt = read_flow(paths[2]) if len(paths) >= 3 else None
@@ -309,9 +320,10 @@ class Net(object):
                 logfile.close()
         return flows
 
-    def _infer_pairs(self, chunk, batch_size):
+    def _infer_pairs(self, chunk, batch_size, variational_refinement=False):
         """Flows (cropped to each frame's size) of up to `batch_size` list lines, one engine launch per group of
-        equally sized frames; a short group is padded with zero pairs so that one engine serves the whole list."""
+        equally sized frames; a short group is padded with zero pairs so that one engine serves the whole list.
+        With `variational_refinement`, one refinement call per group of equal original size."""
         frames = [self.adapt_x_u8(imread(p[0]), imread(p[1])) for p in chunk]
         out = [None] * len(chunk)
         by_shape = {}
@@ -326,11 +338,33 @@ class Net(object):
             eng = self.engine(n, shape[1], shape[2], uint8_inputs=True)
             eng.set_inputs_u8(a, b, scale)
             eng.launch()
+            if variational_refinement:
+                self._refine_group(eng.outputs['flow'], frames, idxs, out)
+                continue
             pred = eng.outputs['flow'].float().cpu().numpy()
             for j, i in enumerate(idxs):
                 info = frames[i][2]
                 out[i] = self.postproc_y_hat_test(pred[j], (info[-3], info[-2], 2) if info is not None else None).copy()
         return out
+
+    @staticmethod
+    def _refine_group(pred, frames, idxs, out):
+        """Variational refinement of the cropped flows pred[j] of frames[idxs[j]], one call per original size; the
+        frames are read in place from their padded device copies."""
+        from .variational import refine
+        by_size = {}
+        for j, i in enumerate(idxs):
+            info = frames[i][2]
+            size = (info[-3], info[-2]) if info is not None else tuple(frames[i][0].shape[1:3])
+            by_size.setdefault(size, []).append((j, i))
+        for (h, w), members in by_size.items():
+            js = torch.tensor([j for j, _ in members], device=pred.device)
+            flow = pred.float().index_select(0, js)[:, :h, :w]
+            a = torch.from_numpy(np.stack([frames[i][0][0] for _, i in members])).to(pred.device)
+            b = torch.from_numpy(np.stack([frames[i][1][0] for _, i in members])).to(pred.device)
+            res = refine(flow, a[:, :h, :w], b[:, :h, :w]).cpu().numpy()
+            for k, (_, i) in enumerate(members):
+                out[i] = res[k]
 
     @staticmethod
     def _average_metrics(table, counts):

@@ -432,6 +432,27 @@ int fn2_augment_f32(const float* src, const float* transforms, const float* chro
 int fn2_flow_augmentation_f32(const float* flows, const float* transforms_from_a, const float* inv_transforms_from_b,
                               float* out, int n, int src_h, int src_w, int out_h, int out_w, void* stream);
 
+/* ---------------------------------------------------------------- variational refinement (EpicFlow)
+ * The reference's src/SrcVariational binary, which utils.py:542-555 (calc_variational_inference_map) runs on the
+ * network's cropped flow when Net.test / Net.test_batch get variational_refinement (net.py:578-589, :889-901):
+ *   fn2_variational_refine  <- variational()        src/SrcVariational/variational.c:101-142
+ *                              compute_one_level()  variational.c:19-82
+ *                              image_warp, get_derivatives, compute_smoothness, sub_laplacian,
+ *                              compute_dpsis_weight, compute_data_and_match   variational_aux.c:18-302
+ *                              sor_coupled          solver.c:57-399 (lexicographic SOR, kept lexicographic)
+ *                              gaussian_filter + color_image_convolve_hv      image.c:116-491
+ * Refines n flows of one size in place.  img_a / img_b: uint8 RGB frames (NHWC; img_pitch bytes between rows,
+ * img_bstride bytes between pairs), read as 0..255 floats; a padded buffer can be passed with its own pitch.
+ * flow: float32 [n][h][w][2] with flow_pitch floats between rows and flow_bstride floats between pairs.
+ * alpha .. sor_omega are variational_params_t (variational_params_default: 1, 0.71, 0, 1, 5, 1, 30, 1.9).
+ * niter_* >= 0, 0 < sigma < 31 / 3.  w < 2 or h < 2 use the reference's readable SOR form (its slow path).
+ * workspace: fn2_variational_workspace_bytes(n, h, w) bytes of device memory (-1 for a bad size). */
+int64_t fn2_variational_workspace_bytes(int n, int h, int w);
+int fn2_variational_refine(const uint8_t* img_a, const uint8_t* img_b, int64_t img_pitch, int64_t img_bstride,
+                           float* flow, int64_t flow_pitch, int64_t flow_bstride, int n, int h, int w, float alpha,
+                           float gamma, float delta, float sigma, int niter_outer, int niter_inner, int niter_solver,
+                           float sor_omega, void* workspace, int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- launch-graph helpers (hipGraph) */
 int fn2_capture_begin(void* stream);
 int fn2_capture_end(void* stream, void** graph_exec);
