@@ -140,6 +140,56 @@ static int check_out16(const fn2_tensor* out, int c, const char* what) {
 
 using namespace fn2;
 
+// FlowNetS_interp stem input from the bytes the files decode to: [image rgb | 0.05 * sparse_flow uv | matches | 0 0]
+// (flownet_s_interp.py:34-38) in the interior of the padded 8-channel stem view -- the view, border and storage formats
+// of pack_image_kernel<OutT, 2> (conv.hip).  The byte -> float step is the table of u8_to_f32_lut_kernel
+// (float32(float64(i) / 255.0)): adapt_x's `/ 255.0` (net.py:334-345) per input whose max exceeds 1, which the
+// per-sample flags carry (flags[2n]: image, flags[2n+1]: mask; cleared = the byte as it is, float32(i)).  The flags are
+// read from device memory, so one captured launch serves any mix of samples.  HBM-bound: 12 bytes in, one 8-channel
+// group out per lane (one 16-byte store for the 16-bit formats, two for the 4-byte ones); the 64 lanes of a wave read
+// 192 + 64 contiguous image / mask bytes and 512 contiguous bytes of sparse flow.
+template <typename OutT>
+__global__ void __launch_bounds__(256) pack_interp_u8_kernel(const unsigned char* __restrict__ img,
+                                                             const unsigned char* __restrict__ mask,
+                                                             const float* __restrict__ sparse,
+                                                             const float* __restrict__ lut,
+                                                             const unsigned char* __restrict__ flags,
+                                                             OutT* __restrict__ out, int n, int h, int w, int pad,
+                                                             int out_cs, int c0) {
+  __shared__ float t[512];  // [0, 256): the byte as it is; [256, 512): the byte / 255 -- a flag is an offset, not a branch
+  t[threadIdx.x] = (float)threadIdx.x;
+  t[256 + threadIdx.x] = lut[threadIdx.x];
+  __syncthreads();
+  const unsigned npix = (unsigned)n * h * w;  // < 2^31 (checked by the caller): 32-bit index arithmetic
+  const int hp = h + 2 * pad, wp = w + 2 * pad;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+    const unsigned row = i / (unsigned)w;
+    const int x = (int)(i - row * w), nn = (int)(row / (unsigned)h), y = (int)(row - nn * h);
+    const unsigned char* p = img + (size_t)i * 3;
+    const unsigned r = p[0], g = p[1], b = p[2], m = mask[i];
+    const float2 sf = *reinterpret_cast<const float2*>(sparse + (size_t)i * 2);
+    const unsigned ti = flags[2 * nn] ? 256u : 0u, tm = flags[2 * nn + 1] ? 256u : 0u;
+    float v[8];
+    v[0] = t[ti + r];
+    v[1] = t[ti + g];
+    v[2] = t[ti + b];
+    v[3] = sf.x * 0.05f;  // flownet_s_interp.py:36
+    v[4] = sf.y * 0.05f;
+    v[5] = t[tm + m];
+    v[6] = v[7] = 0.f;
+    OutT* d = out + (((size_t)nn * hp + y + pad) * wp + x + pad) * out_cs + c0;
+    if constexpr (is_x2<OutT>::value) {
+      uint4* q = reinterpret_cast<uint4*>(d);
+      split8(v, q[0], q[1]);
+    } else if constexpr (sizeof(OutT) == 2) {
+      store_vec<OutT, 8>(d, v);
+    } else {
+      store_vec<OutT, 4>(d, v);
+      store_vec<OutT, 4>(d + 4, v + 4);
+    }
+  }
+}
+
 // uint8 image bytes -> fp32 through a 256-entry table: what Net.adapt_x does on the host (src/net.py:338-345:
 // `x / 255.0` in float64 when the image's max exceeds 1, else the values as they are, then the float32 feed) done
 // after the copy, so the host link carries one byte per channel instead of four.  The table IS the host arithmetic
@@ -173,6 +223,39 @@ int fn2_u8_to_f32_lut(const unsigned char* src, const float* lut256, float* dst,
   hipLaunchKernelGGL(u8_to_f32_lut_kernel, dim3(grid_for(count >> 4, 256)), dim3(256), 0, (hipStream_t)stream, src,
                      lut256, dst, count);
   FN2_CHECK_LAUNCH("u8_to_f32_lut");
+  return FN2_OK;
+}
+
+int fn2_pack_interp_u8(const unsigned char* img, const unsigned char* mask, const float* sparse, const float* lut256,
+                       const unsigned char* flags, const fn2_tensor* out, int pad, void* stream) {
+  FN2_REQUIRE(img && mask && sparse && lut256 && flags, "pack_interp_u8: null pointer");
+  FN2_REQUIRE(out && out->data, "pack_interp_u8: null output");
+  FN2_REQUIRE(out->dtype >= FN2_F32 && out->dtype <= FN2_F16X2, "pack_interp_u8: bad dtype");
+  FN2_REQUIRE(out->n >= 1 && out->c == 6, "pack_interp_u8: output view must have 6 channels");
+  FN2_REQUIRE(out->c0 >= 0 && out->c0 % 8 == 0 && out->cs % 8 == 0 && out->c0 + 8 <= out->cs,
+              "pack_interp_u8: needs an 8-channel aligned slot");
+  FN2_REQUIRE(pad >= 0 && out->h > 2 * pad && out->w > 2 * pad, "pack_interp_u8: bad border");
+  // the 8-byte sparse-flow load and the 16-byte group stores
+  FN2_REQUIRE(((size_t)sparse & 7) == 0 && ((size_t)lut256 & 3) == 0, "pack_interp_u8: sparse must be 8-byte aligned");
+  FN2_REQUIRE(((size_t)out->data & 15) == 0, "pack_interp_u8: output must be 16-byte aligned");
+  const int h = out->h - 2 * pad, w = out->w - 2 * pad;
+  const long npix = (long)out->n * h * w;
+  FN2_REQUIRE(npix < (1L << 31), "pack_interp_u8: more than 2^31 pixels");
+  const dim3 g(grid_for(npix, 256)), b(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (out->dtype == FN2_F32)
+    hipLaunchKernelGGL(pack_interp_u8_kernel<float>, g, b, 0, s, img, mask, sparse, lut256, flags, (float*)out->data,
+                       out->n, h, w, pad, out->cs, out->c0);
+  else if (out->dtype == FN2_F16X2)
+    hipLaunchKernelGGL(pack_interp_u8_kernel<x2_t>, g, b, 0, s, img, mask, sparse, lut256, flags, (x2_t*)out->data,
+                       out->n, h, w, pad, out->cs, out->c0);
+  else if (out->dtype == FN2_BF16)
+    hipLaunchKernelGGL(pack_interp_u8_kernel<bf16_t>, g, b, 0, s, img, mask, sparse, lut256, flags, (bf16_t*)out->data,
+                       out->n, h, w, pad, out->cs, out->c0);
+  else
+    hipLaunchKernelGGL(pack_interp_u8_kernel<f16_t>, g, b, 0, s, img, mask, sparse, lut256, flags, (f16_t*)out->data,
+                       out->n, h, w, pad, out->cs, out->c0);
+  FN2_CHECK_LAUNCH("pack_interp_u8");
   return FN2_OK;
 }
 

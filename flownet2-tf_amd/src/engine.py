@@ -81,10 +81,16 @@ class Engine:
     MAX_TENSOR_BYTES = 1 << 31   # fn2_conv2d refuses larger views (conv.hip: FN2_REQUIRE on in_bytes)
 
     def __init__(self, model, weights, batch, height, width, dtype="f32", device=None, heads_as_gemm=True,
-                 no_deconv_biases=None, strict=True, uint8_inputs=False, plain_stems=False, fragment_weights=None):
+                 no_deconv_biases=None, strict=True, uint8_inputs=False, plain_stems=False, fragment_weights=None,
+                 interp_u8_inputs=False):
         """uint8_inputs: the plan starts with two table look-up passes that turn uint8 image bytes (set_inputs_u8) into
         the fp32 [0,1] images -- Net.adapt_x's `/ 255.0` (net.py:338-345) after the host-to-device copy instead of
         before it, byte-identical, a quarter of the bytes over the host link.
+        interp_u8_inputs (FlowNetS_interp only): the stem input is formed by ONE launch, fn2_pack_interp_u8, from the uint8
+        image and match mask, the fp32 sparse flow and per-sample scale flags (set_inputs_interp_u8) -- adapt_x's `/ 255.0`
+        of image and mask, the graph's `0.05 * sparse_flow` and the concat (flownet_s_interp.py:34-38) -- in place of
+        fn2_pack_pair on host-prepared floats: 12 instead of 24 bytes per pixel over the host link, nothing allocated
+        between the copies and the plan.
         no_deconv_biases: FlowNetS_interp's constructor flag (flownet_s_interp.py:12-14); None = what the weights say
         (no ``FlowNetS/predict_flow6/biases`` entry -> True).  strict: a variable under the model's scopes that no
         layer consumes raises ValueError (optimizer slots and biases the reference graph does not declare excepted:
@@ -160,6 +166,15 @@ class Engine:
                 self.ops.append((f"input_{nm}/u8_to_f32", self.lib.fn2_u8_to_f32_lut,
                                  (_hip.ptr(src), _hip.ptr(lut), _hip.ptr(dst), cnt)))
                 self.branch_of.append(0)
+        self.interp_u8_inputs = bool(interp_u8_inputs)
+        if self.interp_u8_inputs:
+            if model != "FlowNetS_interp":
+                raise ValueError("interp_u8_inputs belongs to FlowNetS_interp, not %s" % model)
+            self.in_img_u8 = torch.zeros((self.N, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
+            self.in_mask_u8 = torch.zeros((self.N, self.H, self.W), dtype=torch.uint8, device=self.device)
+            self.in_sparse = torch.zeros((self.N, self.H, self.W, 2), dtype=torch.float32, device=self.device)
+            self.in_flags = torch.ones((self.N, 2), dtype=torch.uint8, device=self.device)  # per sample: divide image, mask
+            self._lut_255 = torch.from_numpy((np.arange(256, dtype=np.float64) / 255.0).astype(np.float32)).to(self.device)
         self.graph = None
         self.conv_descs = []
         self.layers = []   # one record per parameterised layer, in forward order (used by the trainer)
@@ -913,6 +928,10 @@ class Engine:
         x = self._buf(f"{tag}/pair", self.N, self.H + 2 * pad, self.W + 2 * pad, 6, stem=True)
         v = self._v(x, 6, 0)
         self.keep.append(v)
+        if self.interp_u8_inputs:
+            self._op(f"{tag}/pack_interp_u8", self.lib.fn2_pack_interp_u8, _hip.ptr(self.in_img_u8), _hip.ptr(self.in_mask_u8),
+                     _hip.ptr(self.in_sparse), _hip.ptr(self._lut_255), _hip.ptr(self.in_flags), C.byref(v), pad)
+            return x
         self._op(f"{tag}/pack_pair", self.lib.fn2_pack_pair, _hip.ptr(self.in_a), _hip.ptr(self.in_b), C.byref(v), pad)
         return x
 
@@ -1076,6 +1095,30 @@ class Engine:
         if m.ndim == 3:
             m = m[..., None]
         self.set_inputs(dev(input_a), torch.cat([sf * 0.05, m], dim=3))
+
+    def set_inputs_interp_u8(self, input_a, matches_a, sparse_flow, scale_flags):
+        """The FlowNetS_interp inputs as the files hold them, already zero-padded to the engine size: uint8 image [N,H,W,3],
+        uint8 match mask [N,H,W] (or [N,H,W,1]), float32 sparse flow [N,H,W,2] (host -- ideally pinned -- or device, torch
+        or numpy), and scale_flags [N,2] (or one pair for every sample): divide the image / the mask of sample n by 255
+        (adapt_x does where the input's max exceeds 1, net.py:334-345).  Copies only; the conversion, the `* 0.05` and
+        the concat are the first launch of the plan."""
+        if not self.interp_u8_inputs:
+            raise ValueError("engine was built without interp_u8_inputs=True")
+        as_t = lambda x: x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        img, m, sf = as_t(input_a), as_t(matches_a), as_t(sparse_flow)
+        if img.dtype != torch.uint8 or m.dtype != torch.uint8:
+            raise ValueError("set_inputs_interp_u8 takes a uint8 image and mask, got %s and %s" % (img.dtype, m.dtype))
+        if sf.dtype != torch.float32:
+            raise ValueError("set_inputs_interp_u8 takes a float32 sparse flow, got %s" % sf.dtype)
+        if m.ndim == 4 and m.shape[3] == 1:
+            m = m[..., 0]
+        fl = torch.as_tensor(np.asarray(scale_flags, dtype=bool).astype(np.uint8))
+        if fl.ndim == 1:
+            fl = fl.expand(self.N, 2)
+        for dst, src in ((self.in_img_u8, img), (self.in_mask_u8, m), (self.in_sparse, sf), (self.in_flags, fl)):
+            if tuple(src.shape) != tuple(dst.shape):
+                raise ValueError("input shape %s != engine shape %s" % (tuple(src.shape), tuple(dst.shape)))
+            dst.copy_(src, non_blocking=True)
 
     def launch(self):
         """Enqueue one forward pass on torch's current stream (no host sync)."""

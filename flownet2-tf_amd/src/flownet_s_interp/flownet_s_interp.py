@@ -3,7 +3,10 @@ src/flownet_s_interp/flownet_s_interp.py:10-254): the FlowNetS tower fed with th
 of a set of matches (scaled by 0.05) and the match mask -- flow interpolation instead of flow estimation.
 Variable scope stays 'FlowNetS' (:23), so FlowNetS checkpoints load; with no_deconv_biases (the class default)
 the predict_flow layers carry no biases (:86-95).  The graph runs on the HIP engine (src/engine.py)."""
-from ..net import Net, Mode
+import numpy as np
+import torch
+
+from ..net import Net, Mode, _is_u8
 from .. import weights as W
 from ..losses import multiscale_hfem_loss
 
@@ -27,11 +30,21 @@ class FlowNetS_interp(Net):
 
     def model(self, inputs, training_schedule=None, trainable=True, is_training=True):
         """inputs: {'input_a' [N,H,W,3], 'matches_a' [N,H,W,1], 'sparse_flow' [N,H,W,2]}; is_training=False returns
-        only {'flow'} like the reference (:146-156)."""
-        a = inputs['input_a']
+        only {'flow'} like the reference (:146-156).  A uint8 image with a uint8 mask (Net.adapt_x_matches_u8) goes to the
+        device as bytes and is normalised there; inputs['scale'] may carry adapt_x's per-sample decisions, [N][2] =
+        (divide the image, divide the mask), else they are taken from the samples' maxima."""
+        a, m = inputs['input_a'], inputs['matches_a']
         n, h, w, _ = a.shape
-        eng = self.engine(int(n), int(h), int(w))
-        eng.set_inputs_interp(a, inputs['matches_a'], inputs['sparse_flow'])
+        if _is_u8(a) and _is_u8(m):
+            scale = inputs.get('scale')
+            if scale is None:
+                scale = [(int(a[i].max()) > 1, int(m[i].max()) > 1) for i in range(int(n))]
+            eng = self.engine(int(n), int(h), int(w), interp_u8_inputs=True)
+            sf = inputs['sparse_flow']
+            eng.set_inputs_interp_u8(a, m, sf if isinstance(sf, torch.Tensor) else np.asarray(sf, np.float32), scale)
+        else:
+            eng = self.engine(int(n), int(h), int(w))
+            eng.set_inputs_interp(a, m, inputs['sparse_flow'])
         eng.launch()
         out = {k: v.clone() for k, v in eng.outputs.items()}
         return out if is_training else {'flow': out['flow']}

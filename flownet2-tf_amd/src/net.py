@@ -67,13 +67,14 @@ class Net(object):
     def _init_weights(self, seed):
         return W.init_weights(self.model_name, seed)
 
-    def engine(self, batch, height, width, uint8_inputs=False):
+    def engine(self, batch, height, width, uint8_inputs=False, interp_u8_inputs=False):
         if self.weights is None:
             self.load_weights()
-        key = (batch, height, width, self.dtype, bool(uint8_inputs))
+        key = (batch, height, width, self.dtype, bool(uint8_inputs), bool(interp_u8_inputs))
         if key not in self._engines:
+            extra = {"interp_u8_inputs": True} if interp_u8_inputs else {}
             self._engines[key] = Engine(self.model_name, self.weights, batch, height, width, self.dtype,
-                                        uint8_inputs=uint8_inputs, **self._engine_kwargs())
+                                        uint8_inputs=uint8_inputs, **extra, **self._engine_kwargs())
         return self._engines[key]
 
     def _engine_kwargs(self):
@@ -183,6 +184,30 @@ class Net(object):
             a, m, sf = np.pad(a, pad), np.pad(m, pad), np.pad(sf, pad)
         return a.astype(np.float32), m.astype(np.float32), sf.astype(np.float32), info
 
+    def adapt_x_matches_u8(self, image, mask, sparse_flow, divisor=64):
+        """adapt_x_matches for a uint8 image and a uint8 match mask without float arithmetic on the host: channel and
+        batch axes + zero padding in the source dtypes, and the two decisions adapt_x takes (`max() > 1` -> divide by
+        255, net.py:334-345) returned as `scale` for the device to apply (fn2_pack_interp_u8).
+        Returns (image_u8 [1,H,W,3], mask_u8 [1,H,W,1], sparse_f32 [1,H,W,2], original_shape_or_None,
+        (scale_image, scale_mask))."""
+        a, m = np.asarray(image), np.asarray(mask)
+        if a.dtype != np.uint8 or m.dtype != np.uint8:
+            raise ValueError("adapt_x_matches_u8 takes a uint8 image and a uint8 mask")
+        m = m[..., np.newaxis]
+        sf = np.asarray(sparse_flow, np.float32)
+        assert m.shape[:2] == a.shape[:2] and m.shape[2] == 1, (
+            "Mask has invalid dimensions. Should be ({0}, {1}, 1) but are {2}".format(a.shape[0], a.shape[1], m.shape))
+        scale = (bool(a.max() > 1), bool(m.max() > 1))
+        a, m, sf = a[None], m[None], sf[None]
+        h, w = a.shape[1:3]
+        nh, nw = self.get_padded_image_size(h, w, divisor)
+        info = None
+        if (nh, nw) != (h, w):
+            info = a.shape
+            pad = [(0, 0), (0, nh - h), (0, nw - w), (0, 0)]
+            a, m, sf = np.pad(a, pad), np.pad(m, pad), np.pad(sf, pad)
+        return np.ascontiguousarray(a), np.ascontiguousarray(m), np.ascontiguousarray(sf), info, scale
+
     def postproc_y_hat_test(self, pred_flows, adapt_info=None):
         if adapt_info is not None:
             pred_flows = pred_flows[0:adapt_info[-3], 0:adapt_info[-2], :]
@@ -191,8 +216,10 @@ class Net(object):
     # ---- single-pair inference ----------------------------------------------------------------------
     def test(self, checkpoint, input_a_path, input_b_path=None, matches_a_path=None, sparse_flow_path=None,
              out_path='./', input_type='image_pairs', save_image=True, save_flo=True, compute_metrics=True,
-             gt_flow=None, new_par_folder=None, variational_refinement=False):
-        """net.py:484-628.  input_type 'image_matches' (FlowNetS_interp): first image + match mask + sparse flow.
+             gt_flow=None, new_par_folder=None, occ_mask=None, inv_mask=None, variational_refinement=False):
+        """net.py:484-628.  input_type 'image_matches' (FlowNetS_interp): first image + match mask + sparse flow; with a
+        ground truth it prints the MPI-Sintel metrics block (net.py:612-625; `occ_mask` / `inv_mask`: paths of the
+        occlusion and invalid-pixel masks that split it into matched / unmatched regions).
         `variational_refinement` (with `input_b_path`): the cropped flow is refined on the device by the EpicFlow
         energy minimisation (src/variational.py, the reference's defaults) before metrics and outputs, as
         net.py:578-589 does through its external binary."""
@@ -201,9 +228,15 @@ class Net(object):
         if input_type == 'image_matches':
             if matches_a_path is None or sparse_flow_path is None:
                 raise ValueError("input_type 'image_matches' needs matches_a_path and sparse_flow_path")
-            a, m, sf, info = self.adapt_x_matches(imread(input_a_path), imread_gray(matches_a_path),
-                                                  read_flow(sparse_flow_path))
-            preds = self.model({'input_a': a, 'matches_a': m, 'sparse_flow': sf}, LONG_SCHEDULE, trainable=False)
+            img, mask, sparse = imread(input_a_path), imread_gray(matches_a_path), read_flow(sparse_flow_path)
+            if img.dtype == np.uint8 and mask.dtype == np.uint8:
+                # the files' bytes cross the host link as they are; `/ 255.0`, `* 0.05` and the concat run on the device
+                a, m, sf, info, scale = self.adapt_x_matches_u8(img, mask, sparse)
+                inputs = {'input_a': a, 'matches_a': m, 'sparse_flow': sf, 'scale': [scale]}
+            else:
+                a, m, sf, info = self.adapt_x_matches(img, mask, sparse)
+                inputs = {'input_a': a, 'matches_a': m, 'sparse_flow': sf}
+            preds = self.model(inputs, LONG_SCHEDULE, trainable=False)
         else:
             # image files decode to uint8: they cross the host link as bytes and are normalised on the device
             a, b, info, scale = self.adapt_x_u8(imread(input_a_path), imread(input_b_path))
@@ -237,7 +270,12 @@ class Net(object):
             imsave(full.replace('.png', '_norm_gt_max_motion.png'), flow_to_image(flow.copy(), maxflow=max_flow))
         if save_flo:
             write_flow(flow, os.path.join(out_dir, unique_name + '_flow.flo'))
-        if gt is not None:
+        if gt is not None and (input_type == 'image_matches' or occ_mask is not None or inv_mask is not None):
+            occ = imread_gray(occ_mask) if occ_mask is not None else None
+            inv = imread_gray(inv_mask) if inv_mask is not None else None
+            metrics = compute_all_metrics(flow, gt, occ_mask=occ, inv_mask=inv)[0]
+            print(get_metrics(metrics, flow_fname=unique_name))
+        elif gt is not None:
             from .flowlib import endpoint_error
             print("{}: EPE all = {:.4f}".format(unique_name, endpoint_error(flow, gt)))
         return flow
@@ -249,17 +287,20 @@ class Net(object):
     def test_batch(self, checkpoint, image_paths, out_path, input_type='image_pairs', save_image=True, save_flo=True,
                    compute_metrics=True, accumulate_metrics=False, log_metrics2file=True, width=1024, height=436,
                    new_par_folder=None, variational_refinement=False, batch_size=8):
-        """Inference on every line of the text file `image_paths` (net.py:632-1000): a line is
-        `img1 img2 [gt.flo [occ_mask.png [inv_mask.png]]]`.  Outputs per line as Net.test writes them; with a
-        ground truth, the MPI-Sintel metrics block goes to `<list name>_metrics.log` (or stdout), and
-        `accumulate_metrics` appends the sequence averages.  `width`/`height` are kept for signature
-        compatibility (the reference sizes its placeholders with them); frames are padded by their own size.
-        `batch_size` pairs of equal size go through the engine per launch (the reference feeds one pair per
-        sess.run).  `variational_refinement` refines the cropped flows of each group of equally sized frames in one
-        device call (src/variational.py; the reference runs its binary per pair, net.py:889-901).  The
-        'image_matches' input type belongs to FlowNetS_interp and is not built."""
-        if input_type != 'image_pairs':
-            raise NotImplementedError("test_batch: only input_type='image_pairs' (FlowNetS_interp is out of scope)")
+        """Inference on every line of the text file `image_paths` (net.py:632-1000).  input_type 'image_pairs': a line
+        is `img1 img2 [gt.flo [occ_mask.png [inv_mask.png]]]`.  input_type 'image_matches' (FlowNetS_interp): a line is
+        one of the layouts of `matches_line_fields` -- `I1 MM SF [GT [[OCC [INV]] I2]]`: the last field of a 5-, 6- or
+        7-field line is the second image; the reference's `I1 MM SF GT OCC` and `I1 MM SF GT OCC INV` branches are
+        shadowed by those (net.py:773 / :798, :809 / :820) and are unreachable here as well.
+        Outputs per line as Net.test writes them; with a ground truth, the MPI-Sintel metrics block goes to
+        `<list name>_metrics.log` (or stdout), and `accumulate_metrics` appends the sequence averages.
+        `width`/`height` are kept for signature compatibility (the reference sizes its placeholders with them); frames
+        are padded by their own size.  `batch_size` lines of equal padded size go through the engine per launch (the
+        reference feeds one per sess.run).  `variational_refinement` refines the cropped flows of each group of
+        equally sized frames in one device call (src/variational.py; the reference runs its binary per line,
+        net.py:889-901); an 'image_matches' line without a second image comes back unrefined."""
+        if input_type not in ('image_pairs', 'image_matches'):
+            raise NotImplementedError("test_batch: input_type must be 'image_pairs' or 'image_matches', got %r" % (input_type,))
         if self.weights is None:
             self.load_weights(checkpoint)
         with open(image_paths, 'r') as f:
@@ -279,34 +320,24 @@ class Net(object):
         try:
             for start in range(0, len(lines), batch_size):
                 chunk = lines[start:start + batch_size]
-                for paths, flow in zip(chunk, self._infer_pairs(chunk, batch_size, variational_refinement)):
+                if input_type == 'image_matches':
+                    fields = [matches_line_fields(paths) for paths in chunk]
+                    chunk_flows = self._infer_matches(fields, batch_size, variational_refinement)
+                else:
+                    fields = None
+                    chunk_flows = self._infer_pairs(chunk, batch_size, variational_refinement)
+                for k, (paths, flow) in enumerate(zip(chunk, chunk_flows)):
                     flows.append(flow)
-                    assert 2 <= len(paths) <= 5, 'expected: img1 img2 [gt_flow [occ_mask [inv_mask]]]'
-                    gt = read_flow(paths[2]) if len(paths) >= 3 else None
-                    occ = imread_gray(paths[3]) if len(paths) >= 4 and compute_metrics else None
-                    inv = imread_gray(paths[4]) if len(paths) >= 5 and compute_metrics else None
-                    max_flow = np.max(gt) if (compute_metrics and gt is not None) else -1
-                    parent = paths[0].split('/')[-2] if new_par_folder is None else new_par_folder
-                    unique_name = os.path.basename(paths[0])[:-4]
-                    out_dir = os.path.join(out_path, parent)
-                    if save_image or save_flo:
-                        os.makedirs(out_dir, exist_ok=True)
-                    if save_image:
-                        full = os.path.join(out_dir, unique_name + '_viz.png')
-                        imsave(full, flow_to_image(flow.copy()))
-                        imsave(full.replace('.png', '_norm_gt_max_motion.png'), flow_to_image(flow.copy(), maxflow=max_flow))
-                    if save_flo:
-                        write_flow(flow, os.path.join(out_dir, unique_name + '_flow.flo'))
-                    if compute_metrics and gt is not None:
-                        m, *flags = compute_all_metrics(flow, gt, occ_mask=occ, inv_mask=inv)
-                        text = get_metrics(m, flow_fname=unique_name)
-                        if accumulate_metrics:
-                            counts += np.array(flags)
-                            rows.append([m[k] for k in self._METRIC_ORDER])
-                        if logfile is not None:
-                            logfile.write(text)
-                        else:
-                            print(text)
+                    if fields is not None:
+                        gt_path, occ_path, inv_path = fields[k]['gt'], fields[k]['occ'], fields[k]['inv']
+                    else:
+                        assert 2 <= len(paths) <= 5, 'expected: img1 img2 [gt_flow [occ_mask [inv_mask]]]'
+                        gt_path, occ_path, inv_path = (list(paths[2:5]) + [None] * 3)[:3]
+                    m, flags = self._write_line(flow, paths[0], gt_path, occ_path, inv_path, out_path, new_par_folder,
+                                                save_image, save_flo, compute_metrics, logfile)
+                    if m is not None and accumulate_metrics:
+                        counts += np.array(flags)
+                        rows.append([m[k2] for k2 in self._METRIC_ORDER])
             if accumulate_metrics and rows:
                 avg = self._average_metrics(np.array(rows, np.float64).reshape(len(rows), -1), counts)
                 if logfile is not None:
@@ -319,6 +350,36 @@ class Net(object):
             if logfile is not None:
                 logfile.close()
         return flows
+
+    def _write_line(self, flow, first_path, gt_path, occ_path, inv_path, out_path, new_par_folder, save_image, save_flo,
+                    compute_metrics, logfile):
+        """What test_batch leaves behind for one list line, whatever its input type: the two PNGs, the .flo and -- with
+        a ground truth -- the metrics block (to `logfile`, or stdout).  Returns (metrics, flags) of
+        compute_all_metrics, or (None, None)."""
+        gt = read_flow(gt_path) if gt_path is not None else None
+        occ = imread_gray(occ_path) if occ_path is not None and compute_metrics else None
+        inv = imread_gray(inv_path) if inv_path is not None and compute_metrics else None
+        max_flow = np.max(gt) if (compute_metrics and gt is not None) else -1
+        parent = first_path.split('/')[-2] if new_par_folder is None else new_par_folder
+        unique_name = os.path.basename(first_path)[:-4]
+        out_dir = os.path.join(out_path, parent)
+        if save_image or save_flo:
+            os.makedirs(out_dir, exist_ok=True)
+        if save_image:
+            full = os.path.join(out_dir, unique_name + '_viz.png')
+            imsave(full, flow_to_image(flow.copy()))
+            imsave(full.replace('.png', '_norm_gt_max_motion.png'), flow_to_image(flow.copy(), maxflow=max_flow))
+        if save_flo:
+            write_flow(flow, os.path.join(out_dir, unique_name + '_flow.flo'))
+        if not (compute_metrics and gt is not None):
+            return None, None
+        m, *flags = compute_all_metrics(flow, gt, occ_mask=occ, inv_mask=inv)
+        text = get_metrics(m, flow_fname=unique_name)
+        if logfile is not None:
+            logfile.write(text)
+        else:
+            print(text)
+        return m, flags
 
     def _infer_pairs(self, chunk, batch_size, variational_refinement=False):
         """Flows (cropped to each frame's size) of up to `batch_size` list lines, one engine launch per group of
@@ -346,6 +407,53 @@ class Net(object):
                 info = frames[i][2]
                 out[i] = self.postproc_y_hat_test(pred[j], (info[-3], info[-2], 2) if info is not None else None).copy()
         return out
+
+    def _infer_matches(self, fields, batch_size, variational_refinement=False):
+        """_infer_pairs for 'image_matches' lines (`fields`: matches_line_fields records): image, match mask and sparse
+        flow of up to `batch_size` lines of equal padded size through one launch of the uint8 interp engine.  The scale
+        decisions travel per sample (Engine.in_flags), so lines with 0/255 and 0/1 masks share a launch.  With
+        `variational_refinement`, the lines that name a second image are refined on (I1, I2); the others are not."""
+        frames = [self.adapt_x_matches_u8(imread(f['image']), imread_gray(f['matches']), read_flow(f['sparse']))
+                  for f in fields]
+        out = [None] * len(fields)
+        by_shape = {}
+        for i, fr in enumerate(frames):
+            by_shape.setdefault(fr[0].shape, []).append(i)
+        for shape, idxs in by_shape.items():
+            n = batch_size
+            a = np.zeros((n,) + shape[1:], np.uint8)
+            m = np.zeros((n,) + shape[1:3], np.uint8)
+            sf = np.zeros((n,) + shape[1:3] + (2,), np.float32)
+            flags = np.zeros((n, 2), np.uint8)
+            for j, i in enumerate(idxs):
+                a[j], m[j], sf[j], flags[j] = frames[i][0][0], frames[i][1][0, :, :, 0], frames[i][2][0], frames[i][4]
+            eng = self.engine(n, shape[1], shape[2], interp_u8_inputs=True)
+            eng.set_inputs_interp_u8(a, m, sf, flags)
+            eng.launch()
+            slots = [j for j, i in enumerate(idxs) if variational_refinement and fields[i]['image_b'] is not None]
+            if slots:
+                # (padded first frame, padded second frame, info) per line: the records _refine_group reads
+                pairs = {}
+                for i in (idxs[j] for j in slots):
+                    pairs[i] = (frames[i][0], self._pad_like(imread(fields[i]['image_b']), frames[i][0]), frames[i][3])
+                sel = torch.tensor(slots, device=eng.outputs['flow'].device)
+                self._refine_group(eng.outputs['flow'].index_select(0, sel), pairs, list(pairs), out)
+            if len(slots) < len(idxs):
+                pred = eng.outputs['flow'].float().cpu().numpy()
+                for j, i in enumerate(idxs):
+                    if j not in slots:
+                        info = frames[i][3]
+                        out[i] = self.postproc_y_hat_test(pred[j], (info[-3], info[-2], 2) if info is not None else None).copy()
+        return out
+
+    @staticmethod
+    def _pad_like(image, padded):
+        """uint8 frame [H,W,3] zero-padded (bottom / right) to the [1,Hp,Wp,3] shape of `padded`."""
+        img = np.asarray(image)
+        if img.shape[0] > padded.shape[1] or img.shape[1] > padded.shape[2]:
+            raise AssertionError("FATAL: image dimensions do not match. Image 1 has shape: {0}, "
+                                 "Image 2 has shape: {1}".format(padded.shape, img.shape))
+        return np.pad(img, [(0, padded.shape[1] - img.shape[0]), (0, padded.shape[2] - img.shape[1]), (0, 0)])[None]
 
     @staticmethod
     def _refine_group(pred, frames, idxs, out):
@@ -386,6 +494,31 @@ class Net(object):
         if empty0 > 0:
             avg[9] = avg[9] * (divisor[9] / (divisor[9] - empty0))
         return avg
+
+
+_MATCHES_LINE_ASSERT = ('More paths than expected. Expected: I1+I2 (2), I1+MM+SF(3), I1+MM+SF+GTF(4),'
+                        '  I1+MM+SF+GT+OCC_MSK+INVMASK(5 to 6) optionally + 1extra if variational_refinement')
+
+
+def matches_line_fields(paths):
+    """Fields of one 'image_matches' list line, as the reference dispatches them (net.py:718-850; the first branch that
+    matches a field count wins):
+
+        3  I1 MM SF                 5  I1 MM SF GT I2           7  I1 MM SF GT OCC INV I2
+        4  I1 MM SF GT              6  I1 MM SF GT OCC I2
+
+    The last field of a 5-, 6- or 7-field line is the second image, which only variational refinement reads.  The
+    reference also spells out `I1 MM SF GT OCC` (5) and `I1 MM SF GT OCC INV` (6), but those branches sit behind the
+    ones above with the same test and can never run there; they are unreachable here as well.  Any other field count
+    raises the reference's assertion (:718-720).  Returns {'image', 'matches', 'sparse', 'gt', 'occ', 'inv',
+    'image_b'} with None for what the line does not carry."""
+    n = len(paths)
+    assert 3 <= n <= 7, _MATCHES_LINE_ASSERT
+    return {'image': paths[0], 'matches': paths[1], 'sparse': paths[2],
+            'gt': paths[3] if n >= 4 else None,
+            'occ': paths[4] if n >= 6 else None,
+            'inv': paths[5] if n == 7 else None,
+            'image_b': paths[-1] if n >= 5 else None}
 
 
 def _is_u8(x):

@@ -296,6 +296,16 @@ int fn2_u8_to_f32_lut(const unsigned char* src, const float* lut256, float* dst,
  * row-run convolution.  pad = 0 gives a dense tensor.
  * images fp32 [n,h,w,3] x2 -> out view with 6 (pad 8) channels [a | b | 0 0]  (flownet_s.py:24) */
 int fn2_pack_pair(const float* a, const float* b, const fn2_tensor* out, int pad, void* stream);
+/* FlowNetS_interp's stem input from undecoded-to-float inputs, in one launch: out view with 6 (pad 8) channels
+ * [image rgb | 0.05 * sparse_flow uv | matches | 0 0] (flownet_s_interp.py:34-38), same view and border as fn2_pack_pair.
+ * Replaces the host side of Net.adapt_x on (image, matches) -- src/net.py:334-345: `/ 255.0` for each of the two whose max
+ * exceeds 1 -- and the graph's `sparse_flow * 0.05` + tf.concat (flownet_s_interp.py:36-38).
+ * img: uint8 [n,h,w,3]; mask: uint8 [n,h,w]; sparse: fp32 [n,h,w,2], 8-byte aligned; lut256: the table of
+ * fn2_u8_to_f32_lut, float32(float64(i) / 255.0); flags: DEVICE uint8 [n][2] = {divide the image, divide the mask} of
+ * each sample (0: the byte is converted as it is) -- device memory, so that a captured launch serves any mix of samples.
+ * n, h, w are the view's (h, w less the border); out->data 16-byte aligned. */
+int fn2_pack_interp_u8(const unsigned char* img, const unsigned char* mask, const float* sparse, const float* lut256,
+                       const unsigned char* flags, const fn2_tensor* out, int pad, void* stream);
 /* image fp32 [n_img,h,w,3] -> batch rows [n0, n0+n_img) of the out view, 3 (pad 8) channels
  * (the siamese towers of FlowNetC run as one 2N batch, flownet_c.py:30-37) */
 int fn2_pack_image(const float* img, int n_img, const fn2_tensor* out, int n0, int pad, void* stream);

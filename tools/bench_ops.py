@@ -3,6 +3,7 @@
 bytes per sample), events on the launch stream, median of `--rounds` rounds of `--inner` launches.
 
   python tools/bench_ops.py [--batch 8] [--height 384 --width 512] > profiles/rNN_ops_bandwidth.json
+  python tools/bench_ops.py --interp [--batch 8 ...]    only the FlowNetS_interp input op against what it replaces
 """
 import argparse
 import json
@@ -33,6 +34,66 @@ def timed(fn, rounds, inner):
     return float(np.median(ts))
 
 
+def timed_pair(fn_a, fn_b, rounds, inner):
+    """Two alternatives in the same process, alternating round by round: (median, min, max) ms of each."""
+    ts = ([], [])
+    for r in range(rounds + 2):
+        for k, fn in enumerate((fn_a, fn_b)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if r >= 2:
+                ts[k].append(e0.elapsed_time(e1) / inner)
+    return tuple((float(np.median(t)), float(min(t)), float(max(t))) for t in ts)
+
+
+def bench_interp(N, H, W, rounds, inner, rec):
+    """fn2_pack_interp_u8 (uint8 image + uint8 mask + fp32 sparse flow -> split-fp16 stem input) against the sequence it
+    stands in for, with every input already on the device: the torch ops of Engine.set_inputs_interp (`sf * 0.05`, cat,
+    two staging copies) + fn2_pack_pair."""
+    import ctypes as C
+    dev = _hip.require_device()
+    lib, st, P_ = _hip.lib(), _hip.stream_ptr, _hip.ptr
+    g = torch.Generator(device="cpu").manual_seed(1)
+    pad = 3
+    img8 = torch.randint(0, 256, (N, H, W, 3), generator=g, dtype=torch.uint8).to(dev)
+    m8 = ((torch.rand(N, H, W, generator=g) > 0.9).to(torch.uint8) * 255).to(dev)
+    sf = (torch.randn(N, H, W, 2, generator=g) * 8).to(dev) * (m8 > 0)[..., None]
+    lut = torch.from_numpy((np.arange(256, dtype=np.float64) / 255.0).astype(np.float32)).to(dev)
+    flags = torch.ones(N, 2, dtype=torch.uint8, device=dev)
+    a_f, m_f = lut[img8.long()], lut[m8.long()][..., None]          # what adapt_x_matches ships as fp32
+    in_a, in_b = torch.empty_like(a_f), torch.empty_like(a_f)      # the engine's staging tensors
+    stem_new = torch.zeros(N, H + 2 * pad, W + 2 * pad, 8, dtype=torch.float32, device=dev)
+    stem_old = torch.zeros_like(stem_new)
+    v_new, v_old = _hip.view(stem_new, 6, 0, _hip.FN2_F16X2), _hip.view(stem_old, 6, 0, _hip.FN2_F16X2)
+
+    def new():
+        _hip.check(lib.fn2_pack_interp_u8(P_(img8), P_(m8), P_(sf), P_(lut), P_(flags), C.byref(v_new), pad, st()))
+
+    def pack_pair():
+        _hip.check(lib.fn2_pack_pair(P_(in_a), P_(in_b), C.byref(v_old), pad, st()))
+
+    def old():
+        in_a.copy_(a_f, non_blocking=True)
+        in_b.copy_(torch.cat([sf * 0.05, m_f], dim=3), non_blocking=True)
+        pack_pair()
+
+    new(), old()
+    torch.cuda.synchronize()
+    assert torch.equal(stem_new, stem_old), "the two paths must write the same bytes"
+    px = N * H * W
+    (t_new, lo_n, hi_n), (t_old, lo_o, hi_o) = timed_pair(new, old, rounds, inner)
+    rec("pack_interp_u8", t_new, px * (3 + 1 + 8 + 32), "12 B in (rgb bytes, mask byte, sparse flow) + one 32 B group out per pixel; "
+        "min %.5f max %.5f ms over the rounds" % (lo_n, hi_n))
+    rec("set_inputs_interp_device_ops+pack_pair", t_old, px * (16 + 24 + 48 + 56),
+        "what pack_interp_u8 replaces, inputs on the device: mul (8+8 B), cat (12+12), two staging copies (24+24), pack_pair "
+        "(24+32) per pixel, 5 launches; min %.5f max %.5f ms over the rounds" % (lo_o, hi_o))
+    rec("pack_pair", timed(pack_pair, rounds, inner), px * (24 + 32), "the last launch of that sequence by itself")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -40,6 +101,7 @@ def main():
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--interp", action="store_true", help="only fn2_pack_interp_u8 and the sequence it replaces")
     a = ap.parse_args()
     N, H, W = a.batch, a.height, a.width
     dev = _hip.require_device()
@@ -51,6 +113,10 @@ def main():
         out[name] = {"ms": round(ms, 5), "algorithmic_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / ms / 1e6, 1),
                      "frac_of_hbm_peak": round(nbytes / ms / 1e6 / HBM_PEAK, 4), "note": note}
 
+    if a.interp:
+        bench_interp(N, H, W, a.rounds, a.inner, rec)
+        print(json.dumps({"batch": N, "height": H, "width": W, "hbm_peak_GBps": HBM_PEAK, "ops": out}, indent=1))
+        return
     lib, st = _hip.lib(), _hip.stream_ptr
     P_ = _hip.ptr
     buf = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
@@ -107,6 +173,7 @@ def main():
     ms = timed(lambda: _hip.check(lib.fn2_flow_augmentation_f32(P_(gt), P_(tr), P_(tr), P_(fo), N, H, W, oh, ow, st())),
                a.rounds, a.inner)
     rec("flow_augmentation", ms, N * (H * W + oh * ow) * 2 * 4, "flow once + crop")
+    bench_interp(N, H, W, a.rounds, a.inner, rec)
     print(json.dumps({"batch": N, "height": H, "width": W, "hbm_peak_GBps": HBM_PEAK, "ops": out}, indent=1))
 
 
