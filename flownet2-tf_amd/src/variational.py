@@ -79,9 +79,15 @@ def _check(flow, img_a, img_b):
         raise ValueError("refine: flow and images must be on one device")
 
 
+def _row_pitch(t, c):
+    """Elements between the rows of t (4-D, pixels packed).  A single row has no pitch of its own: views of one-row
+    tensors (a transposed column, say) carry whatever stride they were made with."""
+    return t.stride(1) if t.shape[1] > 1 else c * t.shape[2]
+
+
 def _pixel_rows(t, c):
     """t (4-D) if its pixels are packed (c consecutive elements) and its pairs do not overlap, else a copy."""
-    if t.stride(-1) != 1 or t.stride(-2) != c or (t.shape[0] > 1 and t.stride(0) < t.stride(1) * t.shape[1]):
+    if t.stride(-1) != 1 or t.stride(-2) != c or (t.shape[0] > 1 and t.stride(0) < _row_pitch(t, c) * t.shape[1]):
         t = t.contiguous()
     return t
 
@@ -101,7 +107,7 @@ def refine(flow, img_a, img_b, preset=None, inplace=False, **params):
     b4 = img_b.unsqueeze(0) if squeeze else img_b
     n, h, w, _ = f4.shape
     a4, b4 = _pixel_rows(a4, 3), _pixel_rows(b4, 3)
-    if a4.stride() != b4.stride():
+    if (_row_pitch(a4, 3), a4.stride(0)) != (_row_pitch(b4, 3), b4.stride(0)):
         a4, b4 = a4.contiguous(), b4.contiguous()
     work = f4 if inplace else f4.clone()
     work_k = _pixel_rows(work, 2)
@@ -112,7 +118,7 @@ def refine(flow, img_a, img_b, preset=None, inplace=False, **params):
     with torch.cuda.device(work_k.device):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=work_k.device)
         _hip.check(lib.fn2_variational_refine(
-            _hip.ptr(a4), _hip.ptr(b4), a4.stride(1), a4.stride(0), _hip.ptr(work_k), work_k.stride(1),
+            _hip.ptr(a4), _hip.ptr(b4), _row_pitch(a4, 3), a4.stride(0), _hip.ptr(work_k), _row_pitch(work_k, 2),
             work_k.stride(0), n, h, w, float(p["alpha"]), float(p["gamma"]), float(p["delta"]), float(p["sigma"]),
             p["niter_outer"], p["niter_inner"], p["niter_solver"], float(p["sor_omega"]), _hip.ptr(ws), ws_bytes,
             _hip.stream_ptr()))
