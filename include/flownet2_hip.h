@@ -348,7 +348,7 @@ int fn2_fusion_input_pf(const float* a, const float* b, const float* pf_sd, floa
  * Input gradients of the conv layers are fn2_conv2d launches (kind 0 on rotated weights, kind 3,
  * kind 0 k4 s2 for the transposed convs) with `accumulate`. */
 
-/* L = weight * sum_pixels ||pred - label||_2 / n added to *loss_accum (device scalar);
+/* L = weight * sum_pixels ||pred - label||_2 / n ADDED to *loss_accum (device scalar; the caller zeroes it per step);
  * dpred = grad_mult * weight / n * (pred - label) / ||pred - label||  (average_endpoint_error, utils.py:209-224).
  * grad_mult: loss scaling of the split-fp16 trainer (a power of two that keeps the activation gradients inside
  * the fp16 exponent range; removed again by fn2_adam_step's grad_scale), 1 otherwise. */
@@ -359,10 +359,12 @@ int fn2_epe_loss_grad(const float* pred, const float* label, float* dpred, float
  * EPE pixels of the batch and 0 elsewhere; 'edges': 1 + lambda * edges.  L = weight / n * sum w_pix ||pred - label||. */
 int fn2_epe_loss_grad_weighted(const float* pred, const float* label, const float* pixel_weight, float* dpred,
                                float* loss_accum, int n, int h, int w, float weight, float grad_mult, void* stream);
-/* g *= LeakyReLU'(.) evaluated from the layer output y (utils.py:401-405); y, g fp32 channel-slice views.
- * db != NULL: the bias gradient of the same layer in the same pass, db[c] += sum over pixels of the new g. */
+/* g *= LeakyReLU'(.) evaluated from the layer output y (utils.py:401-405: 1 for y > 0, 0.1 for y < 0, 0.55 at +-0); y, g
+ * channel-slice views, both fp32 (c, cs, c0 multiples of 4) or both split fp16 (multiples of 8); y is only read.
+ * db != NULL: the bias gradient of the same layer in the same pass, ADDED: db[c] += sum over pixels of the new g. */
 int fn2_leaky_bwd(const fn2_tensor* y, const fn2_tensor* g, float* db, void* stream);
-/* db[c] += sum over pixels of g (db zeroed by the caller). */
+/* db[c] += sum over pixels of g: ADDED to what db holds (a caller that wants the plain sum zeroes db first); g is only
+ * read.  fp32 views of any channel count; split-fp16 views of c < 8 channels or whole groups (c, cs, c0 multiples of 8). */
 int fn2_bias_grad(const fn2_tensor* g, float* db, void* stream);
 /* dst (split fp16, n logical elements, n % 8 == 0) = scale * (map ? src[map[i]] (0 where map[i] < 0) : src[i]): the
  * forward and backward-data weight copies of the split-fp16 trainer, re-derived from the fp32 master every step
@@ -396,12 +398,15 @@ int fn2_adam_step_multi(const void* table, const int64_t* counts, const float* l
 int fn2_adam_step_multi_dev(const void* table, const int64_t* counts, const float* l2, int n_tensors, const float* hyper,
                             void* stream);
 /* upsample_flowXtoY backward: g = gradient view [n,2h,2w,2] of its output slice, pf its fp32 input [n,h,w,2],
- * w [4][4][2][2]; dpf (+)= input gradient, dw += filter gradient. */
+ * w [4][4][2][2] (ky, kx, o, i).  dpf = the input gradient, ADDED to dpf where accumulate != 0 and overwriting it where
+ * accumulate == 0; dw += the filter gradient, always ADDED. */
 int fn2_upsample_flow_bwd(const fn2_tensor* g, const float* pf, const float* w, float* dpf, float* dw,
                           int accumulate, void* stream);
-/* flow head (3x3 s1 p1, 2 outputs) filter gradient into rows 0,1 of its natural-order packed weight. */
+/* flow head (3x3 s1 p1, 2 outputs) filter gradient, ADDED into rows 0,1 of its natural-order packed weight gradient:
+ * dw[co * kpad + tap * cin_pad + ci] += sum_pix x[pix][ci] * g[pix - (tap - 1)][co] for ci < x->c; the other elements of
+ * dw are not touched.  x: fp32 or split-fp16 view whose buffer holds its channel count rounded up to 4. */
 int fn2_head_bwd_filter(const fn2_tensor* x, const float* g, float* dw, int cin_pad, int kpad, void* stream);
-/* flow head input gradient, ADDED into the view dx: dx[pix][ci] += sum_{tap,co} g[pix-(tap-1)][co] * w[co][tap][ci]. */
+/* flow head input gradient, ADDED into the view dx (fp32 or split fp16): dx[pix][ci] += sum_{tap,co} g[pix-(tap-1)][co] * w[co][tap][ci]. */
 int fn2_head_bwd_data(const float* g, const float* w, const fn2_tensor* dx, int cin_pad, int kpad, void* stream);
 
 /* Filter gradient of one conv layer on the matrix cores (fp32 tensors: fp32 MFMA; split-fp16 tensors: 3 fp16 MFMAs per
@@ -426,7 +431,7 @@ int fn2_conv2d_bwd_filter(const fn2_bwdw_desc* d, void* stream);
  * tap][o] (zero outside the image) into `out` (c == 18, at least 24 channels of room; channels >= 24 of a wider buffer
  * must be zero and stay untouched).  Then fn2_conv2d_bwd_filter with kind 4 (x = head input, dy = G18, dw = the head's
  * natural-order weight gradient [2][kpad], cin_pad, kpad of the head) is the filter gradient, and a 1x1 fn2_conv2d from
- * G18 with accumulate the input gradient.  (fn2_head_bwd_filter / fn2_head_bwd_data are the fp32-tensor forms.) */
+ * G18 with accumulate the input gradient.  (fn2_head_bwd_filter / fn2_head_bwd_data are the direct forms, without G18.) */
 int fn2_head_g18(const float* g, const fn2_tensor* out, void* stream);
 
 /* ---------------------------------------------------------------- training-input augmentation
