@@ -16,6 +16,7 @@ FN2_F32, FN2_BF16, FN2_F16, FN2_F16X2 = 0, 1, 2, 3
 ACT_NONE, ACT_LEAKY = 0, 1
 OK = 0
 ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3
+MASK_F32, MASK_U8 = 0, 1
 
 
 class Fn2Tensor(C.Structure):
@@ -108,6 +109,8 @@ PROTOTYPES = {
     "fn2_variational_workspace_bytes": (C.c_int64, [_i, _i, _i]),
     "fn2_variational_refine": (_i, [_p, _p, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int64, _i, _i, _i, _f, _f, _f, _f,
                                     _i, _i, _i, _f, _p, C.c_int64, _p]),
+    "fn2_tf_warp_f32": (_i, [_p, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int64, _p, _i, _i, _i, _i, _p]),
+    "fn2_fb_occlusion": (_i, [_p, _p, C.c_int64, C.c_int64, _p, _p, _i, _i, _i, _i, _f, _f, _p]),
     "fn2_capture_begin": (_i, [_p]),
     "fn2_capture_end": (_i, [_p, C.POINTER(C.c_void_p)]),
     "fn2_graph_launch": (_i, [_p, _p]),

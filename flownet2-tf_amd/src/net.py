@@ -216,13 +216,20 @@ class Net(object):
     # ---- single-pair inference ----------------------------------------------------------------------
     def test(self, checkpoint, input_a_path, input_b_path=None, matches_a_path=None, sparse_flow_path=None,
              out_path='./', input_type='image_pairs', save_image=True, save_flo=True, compute_metrics=True,
-             gt_flow=None, new_par_folder=None, occ_mask=None, inv_mask=None, variational_refinement=False):
+             gt_flow=None, new_par_folder=None, occlusions=False, occ_mask=None, inv_mask=None,
+             variational_refinement=False):
         """net.py:484-628.  input_type 'image_matches' (FlowNetS_interp): first image + match mask + sparse flow; with a
         ground truth it prints the MPI-Sintel metrics block (net.py:612-625; `occ_mask` / `inv_mask`: paths of the
         occlusion and invalid-pixel masks that split it into matched / unmatched regions).
         `variational_refinement` (with `input_b_path`): the cropped flow is refined on the device by the EpicFlow
         energy minimisation (src/variational.py, the reference's defaults) before metrics and outputs, as
-        net.py:578-589 does through its external binary."""
+        net.py:578-589 does through its external binary.
+        `occlusions` ('image_pairs' only): the pair runs in both directions in one launch and the forward-backward check
+        (src/occlusion.py) writes `<name>_occ.png`, `<name>_occ_bw.png` (0 / 255) and `<name>_flow_bw.flo` next to the usual
+        outputs; the masks are kept in `self.last_occlusions`.  The return value stays the forward flow."""
+        if occlusions and input_type == 'image_matches':
+            raise ValueError("occlusions need the second frame as a network input: input_type 'image_matches' has no "
+                             "matches for it")
         if self.weights is None:
             self.load_weights(checkpoint)
         if input_type == 'image_matches':
@@ -237,12 +244,20 @@ class Net(object):
                 a, m, sf, info = self.adapt_x_matches(img, mask, sparse)
                 inputs = {'input_a': a, 'matches_a': m, 'sparse_flow': sf}
             preds = self.model(inputs, LONG_SCHEDULE, trainable=False)
+        elif occlusions:
+            # both directions in the two slots of one launch; the forward flow is refined after the masks are formed
+            flow, flow_bw, occ_fw, occ_bw = self._infer_pairs([[input_a_path, input_b_path]], 2, variational_refinement,
+                                                              bidirectional=True)[0]
+            self.last_occlusions = [(occ_fw, occ_bw)]
+            preds = info = None  # cropped (and refined) already
         else:
             # image files decode to uint8: they cross the host link as bytes and are normalised on the device
             a, b, info, scale = self.adapt_x_u8(imread(input_a_path), imread(input_b_path))
             preds = self.model({'input_a': a, 'input_b': b, 'scale': scale}, LONG_SCHEDULE, trainable=False)
         y_info = (info[-3], info[-2], 2) if info is not None else None
-        if variational_refinement and input_b_path is not None:
+        if preds is None:
+            pass
+        elif variational_refinement and input_b_path is not None:
             from .variational import refine
             pred = self.postproc_y_hat_test(preds['flow'][0].float(), y_info)
             dev = pred.device
@@ -270,6 +285,8 @@ class Net(object):
             imsave(full.replace('.png', '_norm_gt_max_motion.png'), flow_to_image(flow.copy(), maxflow=max_flow))
         if save_flo:
             write_flow(flow, os.path.join(out_dir, unique_name + '_flow.flo'))
+        if occlusions:
+            self._write_occlusions(out_dir, unique_name, flow_bw, occ_fw, occ_bw)
         if gt is not None and (input_type == 'image_matches' or occ_mask is not None or inv_mask is not None):
             occ = imread_gray(occ_mask) if occ_mask is not None else None
             inv = imread_gray(inv_mask) if inv_mask is not None else None
@@ -286,7 +303,8 @@ class Net(object):
 
     def test_batch(self, checkpoint, image_paths, out_path, input_type='image_pairs', save_image=True, save_flo=True,
                    compute_metrics=True, accumulate_metrics=False, log_metrics2file=True, width=1024, height=436,
-                   new_par_folder=None, variational_refinement=False, batch_size=8):
+                   new_par_folder=None, variational_refinement=False, batch_size=8, occlusions=False,
+                   occlusions_for_metrics=False):
         """Inference on every line of the text file `image_paths` (net.py:632-1000).  input_type 'image_pairs': a line
         is `img1 img2 [gt.flo [occ_mask.png [inv_mask.png]]]`.  input_type 'image_matches' (FlowNetS_interp): a line is
         one of the layouts of `matches_line_fields` -- `I1 MM SF [GT [[OCC [INV]] I2]]`: the last field of a 5-, 6- or
@@ -298,9 +316,24 @@ class Net(object):
         are padded by their own size.  `batch_size` lines of equal padded size go through the engine per launch (the
         reference feeds one per sess.run).  `variational_refinement` refines the cropped flows of each group of
         equally sized frames in one device call (src/variational.py; the reference runs its binary per line,
-        net.py:889-901); an 'image_matches' line without a second image comes back unrefined."""
+        net.py:889-901); an 'image_matches' line without a second image comes back unrefined.
+        `occlusions` / `occlusions_for_metrics` ('image_pairs' only, `batch_size` even): every line runs in both
+        directions -- (a, b) in slot 2k and (b, a) in slot 2k + 1 of the same `batch_size` engine, so `batch_size // 2`
+        lines per launch -- and the forward-backward check (src/occlusion.py) gives an occlusion mask per direction, kept
+        as `self.last_occlusions` [(occ_fw, occ_bw) uint8 0 / 255 per line].  With `occlusions` a line also writes
+        `<name>_occ.png`, `<name>_occ_bw.png` and `<name>_flow_bw.flo`; with `occlusions_for_metrics` a line with a ground
+        truth and no occlusion mask file takes the estimated forward mask for the matched / unmatched split of its
+        metrics.  The return value stays the forward flows; with `variational_refinement` only those are refined, after
+        the masks are formed."""
         if input_type not in ('image_pairs', 'image_matches'):
             raise NotImplementedError("test_batch: input_type must be 'image_pairs' or 'image_matches', got %r" % (input_type,))
+        bidirectional = bool(occlusions or occlusions_for_metrics)
+        if bidirectional and input_type == 'image_matches':
+            raise ValueError("occlusions need the second frame as a network input: input_type 'image_matches' has no "
+                             "matches for it")
+        if bidirectional and batch_size % 2:
+            raise ValueError("occlusions put the two directions of a line into neighbouring slots: batch_size must be "
+                             "even, got %d" % batch_size)
         if self.weights is None:
             self.load_weights(checkpoint)
         with open(image_paths, 'r') as f:
@@ -317,16 +350,27 @@ class Net(object):
                     datetime.datetime.now().strftime('%d-%m-%y_%H-%M-%S'), new_par_folder, full))
         rows, counts = [], np.zeros(4, np.int64)  # not occluded / empty S0-10 / S10-40 / S40+ frame counts
         flows = []
+        if bidirectional:
+            self.last_occlusions = []
+        per_launch = batch_size // 2 if bidirectional else batch_size
         try:
-            for start in range(0, len(lines), batch_size):
-                chunk = lines[start:start + batch_size]
+            for start in range(0, len(lines), per_launch):
+                chunk = lines[start:start + per_launch]
                 if input_type == 'image_matches':
                     fields = [matches_line_fields(paths) for paths in chunk]
                     chunk_flows = self._infer_matches(fields, batch_size, variational_refinement)
                 else:
                     fields = None
-                    chunk_flows = self._infer_pairs(chunk, batch_size, variational_refinement)
+                    chunk_flows = self._infer_pairs(chunk, batch_size, variational_refinement, bidirectional=bidirectional)
                 for k, (paths, flow) in enumerate(zip(chunk, chunk_flows)):
+                    extra = {}
+                    if bidirectional:
+                        flow, flow_bw, occ_fw, occ_bw = flow
+                        self.last_occlusions.append((occ_fw, occ_bw))
+                        if occlusions:
+                            extra['occlusions'] = (flow_bw, occ_fw, occ_bw)
+                        if occlusions_for_metrics:
+                            extra['estimated_occ'] = occ_fw
                     flows.append(flow)
                     if fields is not None:
                         gt_path, occ_path, inv_path = fields[k]['gt'], fields[k]['occ'], fields[k]['inv']
@@ -334,7 +378,7 @@ class Net(object):
                         assert 2 <= len(paths) <= 5, 'expected: img1 img2 [gt_flow [occ_mask [inv_mask]]]'
                         gt_path, occ_path, inv_path = (list(paths[2:5]) + [None] * 3)[:3]
                     m, flags = self._write_line(flow, paths[0], gt_path, occ_path, inv_path, out_path, new_par_folder,
-                                                save_image, save_flo, compute_metrics, logfile)
+                                                save_image, save_flo, compute_metrics, logfile, **extra)
                     if m is not None and accumulate_metrics:
                         counts += np.array(flags)
                         rows.append([m[k2] for k2 in self._METRIC_ORDER])
@@ -352,12 +396,15 @@ class Net(object):
         return flows
 
     def _write_line(self, flow, first_path, gt_path, occ_path, inv_path, out_path, new_par_folder, save_image, save_flo,
-                    compute_metrics, logfile):
+                    compute_metrics, logfile, occlusions=None, estimated_occ=None):
         """What test_batch leaves behind for one list line, whatever its input type: the two PNGs, the .flo and -- with
-        a ground truth -- the metrics block (to `logfile`, or stdout).  Returns (metrics, flags) of
-        compute_all_metrics, or (None, None)."""
+        a ground truth -- the metrics block (to `logfile`, or stdout).  `occlusions` (flow_bw, occ_fw, occ_bw): the
+        files of _write_occlusions as well.  `estimated_occ`: the occlusion mask of a line that names no mask file.
+        Returns (metrics, flags) of compute_all_metrics, or (None, None)."""
         gt = read_flow(gt_path) if gt_path is not None else None
         occ = imread_gray(occ_path) if occ_path is not None and compute_metrics else None
+        if occ is None and occ_path is None and compute_metrics:
+            occ = estimated_occ
         inv = imread_gray(inv_path) if inv_path is not None and compute_metrics else None
         max_flow = np.max(gt) if (compute_metrics and gt is not None) else -1
         parent = first_path.split('/')[-2] if new_par_folder is None else new_par_folder
@@ -371,6 +418,8 @@ class Net(object):
             imsave(full.replace('.png', '_norm_gt_max_motion.png'), flow_to_image(flow.copy(), maxflow=max_flow))
         if save_flo:
             write_flow(flow, os.path.join(out_dir, unique_name + '_flow.flo'))
+        if occlusions is not None:
+            self._write_occlusions(out_dir, unique_name, *occlusions)
         if not (compute_metrics and gt is not None):
             return None, None
         m, *flags = compute_all_metrics(flow, gt, occ_mask=occ, inv_mask=inv)
@@ -381,10 +430,13 @@ class Net(object):
             print(text)
         return m, flags
 
-    def _infer_pairs(self, chunk, batch_size, variational_refinement=False):
+    def _infer_pairs(self, chunk, batch_size, variational_refinement=False, bidirectional=False):
         """Flows (cropped to each frame's size) of up to `batch_size` list lines, one engine launch per group of
         equally sized frames; a short group is padded with zero pairs so that one engine serves the whole list.
-        With `variational_refinement`, one refinement call per group of equal original size."""
+        With `variational_refinement`, one refinement call per group of equal original size.
+        `bidirectional`: up to `batch_size // 2` lines, see _infer_bidirectional."""
+        if bidirectional:
+            return self._infer_bidirectional(chunk, batch_size, variational_refinement)
         frames = [self.adapt_x_u8(imread(p[0]), imread(p[1])) for p in chunk]
         out = [None] * len(chunk)
         by_shape = {}
@@ -407,6 +459,75 @@ class Net(object):
                 info = frames[i][2]
                 out[i] = self.postproc_y_hat_test(pred[j], (info[-3], info[-2], 2) if info is not None else None).copy()
         return out
+
+    def _infer_bidirectional(self, chunk, batch_size, variational_refinement=False):
+        """(flow_fw, flow_bw, occ_fw, occ_bw) of up to `batch_size // 2` list lines: flows [h,w,2] float32 and
+        forward-backward occlusion masks [h,w] uint8 0 / 255 (src/occlusion.py), cropped to each frame's size.  Line k
+        of a group of equally sized frames fills slot 2k with (a, b) and slot 2k + 1 with (b, a) of the `batch_size`
+        engine _infer_pairs uses: the backward flows ride on the launch that is running anyway.  Both flows are cropped
+        on the device and the check reads the crops in place, one call per run of neighbouring lines of equal
+        original size.  With `variational_refinement` the forward flow is refined, after the masks are formed."""
+        from .occlusion import occlusion
+        if batch_size % 2:
+            raise ValueError("bidirectional inference puts the two directions of a line into neighbouring slots: "
+                             "batch_size must be even, got %d" % batch_size)
+        if len(chunk) > batch_size // 2:
+            raise ValueError("bidirectional inference takes batch_size // 2 = %d lines per launch, got %d"
+                             % (batch_size // 2, len(chunk)))
+        frames = [self.adapt_x_u8(imread(p[0]), imread(p[1])) for p in chunk]
+        out = [None] * len(chunk)
+        by_shape = {}
+        for i, (a, _, _, scale) in enumerate(frames):
+            by_shape.setdefault((a.shape, scale), []).append(i)
+        for (shape, scale), idxs in by_shape.items():
+            a = np.zeros((batch_size,) + shape[1:], np.uint8)
+            b = np.zeros_like(a)
+            for k, i in enumerate(idxs):
+                a[2 * k], b[2 * k] = frames[i][0][0], frames[i][1][0]
+                a[2 * k + 1], b[2 * k + 1] = frames[i][1][0], frames[i][0][0]
+            eng = self.engine(batch_size, shape[1], shape[2], uint8_inputs=True)
+            eng.set_inputs_u8(a, b, scale)
+            eng.launch()
+            flow = eng.outputs['flow'].float()
+            if scale[0] != scale[1]:
+                # an input buffer has one normalisation decision per launch and the two frames disagree: the odd slots
+                # come from a second launch with the decisions swapped
+                flow = flow.clone()
+                eng.set_inputs_u8(a, b, scale[::-1])
+                eng.launch()
+                flow[1::2] = eng.outputs['flow'][1::2].float()
+            sizes = []
+            for i in idxs:
+                info = frames[i][2]
+                sizes.append((info[-3], info[-2]) if info is not None else tuple(shape[1:3]))
+            k = 0
+            while k < len(idxs):
+                m = 1
+                while k + m < len(idxs) and sizes[k + m] == sizes[k]:
+                    m += 1
+                h, w = sizes[k]
+                fw = flow[2 * k:2 * (k + m):2, :h, :w]
+                bw = flow[2 * k + 1:2 * (k + m):2, :h, :w]
+                occ_fw, occ_bw = (t.cpu().numpy()[..., 0] for t in occlusion(fw, bw, as_uint8=True))
+                fw, bw = fw.cpu().numpy(), bw.cpu().numpy()
+                for j in range(m):
+                    out[idxs[k + j]] = (np.ascontiguousarray(fw[j]), np.ascontiguousarray(bw[j]),
+                                        np.ascontiguousarray(occ_fw[j]), np.ascontiguousarray(occ_bw[j]))
+                k += m
+            if variational_refinement:
+                refined = [None] * len(chunk)
+                self._refine_group(flow[0::2], frames, idxs, refined)
+                for i in idxs:
+                    out[i] = (refined[i],) + out[i][1:]
+        return out
+
+    @staticmethod
+    def _write_occlusions(out_dir, unique_name, flow_bw, occ_fw, occ_bw):
+        """`<name>_occ.png` (forward mask, 0 / 255), `<name>_occ_bw.png` and `<name>_flow_bw.flo`."""
+        os.makedirs(out_dir, exist_ok=True)
+        imsave(os.path.join(out_dir, unique_name + '_occ.png'), occ_fw)
+        imsave(os.path.join(out_dir, unique_name + '_occ_bw.png'), occ_bw)
+        write_flow(flow_bw, os.path.join(out_dir, unique_name + '_flow_bw.flo'))
 
     def _infer_matches(self, fields, batch_size, variational_refinement=False):
         """_infer_pairs for 'image_matches' lines (`fields`: matches_line_fields records): image, match mask and sparse
@@ -519,6 +640,18 @@ def matches_line_fields(paths):
             'occ': paths[4] if n >= 6 else None,
             'inv': paths[5] if n == 7 else None,
             'image_b': paths[-1] if n >= 5 else None}
+
+
+def str2bool(v):
+    """argparse type of the CLIs' boolean flags (utils.py str2bool)."""
+    import argparse
+    if isinstance(v, bool):
+        return v
+    if v.lower() in ('yes', 'true', 't', 'y', '1'):
+        return True
+    if v.lower() in ('no', 'false', 'f', 'n', '0'):
+        return False
+    raise argparse.ArgumentTypeError('Boolean value expected.')
 
 
 def _is_u8(x):

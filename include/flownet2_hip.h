@@ -468,6 +468,35 @@ int fn2_variational_refine(const uint8_t* img_a, const uint8_t* img_b, int64_t i
                            float gamma, float delta, float sigma, int niter_outer, int niter_inner, int niter_solver,
                            float sor_omega, void* workspace, int64_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- forward-backward occlusion check
+ * The reference's consistency test between a forward and a backward flow (the SelFlow check), which it carries but
+ * never runs (src/utils.py:424):
+ *   fn2_tf_warp_f32   <- tf_warp          src/utils.py:453-515  (+ get_pixel_value :426-450)
+ *   fn2_fb_occlusion  <- occlusion        src/utils.py:523-538  (+ length_sq :519-520, both tf_warp calls)
+ * tf_warp is a backward bilinear warp with its own index rules -- it is not fn2_flow_warp_f32: the coordinate
+ * (x + u, y + v) is truncated toward zero, the taps t and t + 1 of each axis are clamped to the image after the + 1, and
+ * the four weights (x1 - x)(y1 - y), (x1 - x)(y - y0), (x - x0)(y1 - y), (x - x0)(y - y0) are formed from the clamped
+ * taps and the unclamped coordinate.  Nothing is tested for being in range: x in (-1, 0) extrapolates from columns 0 and
+ * 1, and where both taps of an axis clamp to one index (x <= -1, x >= w - 1, a 1-wide image) the result is exactly 0.
+ * The float-to-int conversion saturates and takes NaN to 0, so no tap leaves the image whatever the flow holds; what is
+ * written at a pixel whose coordinate is not finite is unspecified.
+ * Pitches (between rows) and batch strides (between images) are in floats, as in fn2_variational_refine: a crop of a
+ * padded buffer is passed as it lies.  Flows are read as 8-byte pairs: base 8-byte aligned, pitch and stride even. */
+
+/* out[n,y,x,:] = tf_warp(img, flow)[n,y,x,:].  img: [n][h][w][c] with img_pitch / img_bstride; flow: [n][h][w][2] with
+ * flow_pitch / flow_bstride; out: dense [n,h,w,c]. */
+int fn2_tf_warp_f32(const float* img, int64_t img_pitch, int64_t img_bstride, const float* flow, int64_t flow_pitch,
+                    int64_t flow_bstride, float* out, int n, int h, int w, int c, void* stream);
+
+/* Both masks in one launch, the warped flows never stored:
+ *   occ_fw = |fw + tf_warp(bw, fw)|^2 > alpha * (|fw|^2 + |tf_warp(bw, fw)|^2) + beta, occ_bw with the roles swapped
+ * (the reference: alpha 0.01, beta 0.5).  flow_fw / flow_bw: [n][h][w][2] sharing flow_pitch / flow_bstride (they may be
+ * two slices of one buffer); occ_fw / occ_bw: dense [n,h,w,1] of mask_dtype -- FN2_MASK_F32: float32 0 / 1, what the
+ * reference returns; FN2_MASK_U8: uint8 0 / 255, what a mask file holds. */
+typedef enum { FN2_MASK_F32 = 0, FN2_MASK_U8 = 1 } fn2_mask_dtype;
+int fn2_fb_occlusion(const float* flow_fw, const float* flow_bw, int64_t flow_pitch, int64_t flow_bstride, void* occ_fw,
+                     void* occ_bw, int mask_dtype, int n, int h, int w, float alpha, float beta, void* stream);
+
 /* ---------------------------------------------------------------- launch-graph helpers (hipGraph) */
 int fn2_capture_begin(void* stream);
 int fn2_capture_end(void* stream, void** graph_exec);

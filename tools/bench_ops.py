@@ -4,6 +4,7 @@ bytes per sample), events on the launch stream, median of `--rounds` rounds of `
 
   python tools/bench_ops.py [--batch 8] [--height 384 --width 512] > profiles/rNN_ops_bandwidth.json
   python tools/bench_ops.py --interp [--batch 8 ...]    only the FlowNetS_interp input op against what it replaces
+  python tools/bench_ops.py --occlusion --batch 4 --height 436 --width 1024    only the forward-backward occlusion check
 """
 import argparse
 import json
@@ -94,6 +95,32 @@ def bench_interp(N, H, W, rounds, inner, rec):
     rec("pack_pair", timed(pack_pair, rounds, inner), px * (24 + 32), "the last launch of that sequence by itself")
 
 
+def bench_occlusion(N, H, W, rounds, inner, rec):
+    """fn2_fb_occlusion on a smooth flow pair (the case its gathers are laid out for: neighbouring lanes read neighbouring
+    taps) and on an incoherent one (every tap its own cache line), and fn2_tf_warp_f32 on a two-channel map.  Algorithmic
+    traffic per pixel: both flows once (16 B) + both masks (8 B as float32, 2 B as uint8); the 8 gathered taps are reuse."""
+    dev = _hip.require_device()
+    lib, st, P_ = _hip.lib(), _hip.stream_ptr, _hip.ptr
+    g = torch.Generator(device="cpu").manual_seed(2)
+    coarse = torch.randn(N, 2, H // 32 + 2, W // 32 + 2, generator=g) * 6
+    smooth = torch.nn.functional.interpolate(coarse, size=(H, W), mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
+    fw = smooth.contiguous().to(dev)
+    bw = (-smooth + 0.3 * torch.randn(N, H, W, 2, generator=g)).contiguous().to(dev)
+    rough_fw, rough_bw = (torch.randn(N, H, W, 2, generator=g) * 40).to(dev), (torch.randn(N, H, W, 2, generator=g) * 40).to(dev)
+    px = N * H * W
+    for tag, (a, b) in (("", (fw, bw)), ("_incoherent", (rough_fw, rough_bw))):
+        for code, name, dt, mb in ((_hip.MASK_F32, "f32", torch.float32, 4), (_hip.MASK_U8, "u8", torch.uint8, 1)):
+            o1, o2 = torch.empty(px, dtype=dt, device=dev), torch.empty(px, dtype=dt, device=dev)
+            ms = timed(lambda: _hip.check(lib.fn2_fb_occlusion(P_(a), P_(b), 2 * W, 2 * W * H, P_(o1), P_(o2), code, N, H, W,
+                                                               0.01, 0.5, st())), rounds, inner)
+            rec("fb_occlusion_%s%s" % (name, tag), ms, px * (16 + 2 * mb),
+                "both flows once + both masks; %.2f of the forward mask set" % float((o1 != 0).float().mean()))
+    wo = torch.empty(N, H, W, 2, dtype=torch.float32, device=dev)
+    ms = timed(lambda: _hip.check(lib.fn2_tf_warp_f32(P_(bw), 2 * W, 2 * W * H, P_(fw), 2 * W, 2 * W * H, P_(wo), N, H, W, 2,
+                                                      st())), rounds, inner)
+    rec("tf_warp_f32_c2", ms, px * (8 + 8 + 8), "map + flow + output")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -102,6 +129,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--interp", action="store_true", help="only fn2_pack_interp_u8 and the sequence it replaces")
+    ap.add_argument("--occlusion", action="store_true", help="only fn2_fb_occlusion and fn2_tf_warp_f32")
     a = ap.parse_args()
     N, H, W = a.batch, a.height, a.width
     dev = _hip.require_device()
@@ -113,8 +141,8 @@ def main():
         out[name] = {"ms": round(ms, 5), "algorithmic_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / ms / 1e6, 1),
                      "frac_of_hbm_peak": round(nbytes / ms / 1e6 / HBM_PEAK, 4), "note": note}
 
-    if a.interp:
-        bench_interp(N, H, W, a.rounds, a.inner, rec)
+    if a.interp or a.occlusion:
+        (bench_interp if a.interp else bench_occlusion)(N, H, W, a.rounds, a.inner, rec)
         print(json.dumps({"batch": N, "height": H, "width": W, "hbm_peak_GBps": HBM_PEAK, "ops": out}, indent=1))
         return
     lib, st = _hip.lib(), _hip.stream_ptr
@@ -174,6 +202,7 @@ def main():
                a.rounds, a.inner)
     rec("flow_augmentation", ms, N * (H * W + oh * ow) * 2 * 4, "flow once + crop")
     bench_interp(N, H, W, a.rounds, a.inner, rec)
+    bench_occlusion(N, H, W, a.rounds, a.inner, rec)
     print(json.dumps({"batch": N, "height": H, "width": W, "hbm_peak_GBps": HBM_PEAK, "ops": out}, indent=1))
 
 
