@@ -7,20 +7,10 @@ anything else is one frame through Net.test.  --checkpoint (.npz), --dtype and -
 import argparse
 import os
 
-from ..net import Mode
+from ..net import Mode, str2bool
 from .flownet_s_interp import FlowNetS_interp
 
 FLAGS = None
-
-
-def str2bool(v):
-    if isinstance(v, bool):
-        return v
-    if v.lower() in ('yes', 'true', 't', 'y', '1'):
-        return True
-    if v.lower() in ('no', 'false', 'f', 'n', '0'):
-        return False
-    raise argparse.ArgumentTypeError('Boolean value expected.')
 
 
 def is_list(path):

@@ -8,6 +8,7 @@ sub-folder is the parent directory name of ``input_a`` (the intended behaviour
 behind defect D3), and a missing checkpoint falls back -- loudly -- to seeded
 synthetic weights, because no trained weights can be obtained offline.
 """
+import datetime
 import os
 import sys
 from enum import Enum
@@ -18,7 +19,7 @@ import torch
 
 from . import weights as W
 from .engine import BatchTooLarge, Engine
-from .flowlib import compute_all_metrics, flow_to_image, get_metrics, read_flow, write_flow
+from .flowlib import compute_all_metrics, endpoint_error, flow_to_image, get_metrics, read_flow, write_flow
 from .training_schedules import LONG_SCHEDULE
 
 
@@ -123,23 +124,10 @@ class Net(object):
     def adapt_x(self, input_a, input_b, divisor=64):
         """[0,255] -> [0,1] when max > 1; add the batch axis; zero-pad bottom/right to a multiple
         of ``divisor``.  Returns (a, b, original_shape_or_None)."""
-        def norm(x):
-            x = np.asarray(x)
-            return x / 255.0 if x.max() > 1.0 else x.astype(np.float64)
-
-        a, b = norm(input_a), norm(input_b)
+        a, b = _unit_range(input_a), _unit_range(input_b)
         if a.shape != b.shape:
-            raise AssertionError("FATAL: image dimensions do not match. Image 1 has shape: {0}, "
-                                 "Image 2 has shape: {1}".format(a.shape, b.shape))
-        if a.ndim == 3:
-            a, b = a[None], b[None]
-        h, w = a.shape[1:3]
-        nh, nw = self.get_padded_image_size(h, w, divisor)
-        info = None
-        if (nh, nw) != (h, w):
-            info = a.shape
-            pad = [(0, 0), (0, nh - h), (0, nw - w), (0, 0)]
-            a, b = np.pad(a, pad), np.pad(b, pad)
+            raise _shapes_differ(a.shape, b.shape)
+        (a, b), info = self._batch_and_pad((a, b), divisor)
         return a.astype(np.float32), b.astype(np.float32), info
 
     def adapt_x_u8(self, input_a, input_b, divisor=64):
@@ -150,38 +138,19 @@ class Net(object):
         if a.dtype != np.uint8 or b.dtype != np.uint8:
             raise ValueError("adapt_x_u8 takes uint8 images")
         if a.shape != b.shape:
-            raise AssertionError("FATAL: image dimensions do not match. Image 1 has shape: {0}, "
-                                 "Image 2 has shape: {1}".format(a.shape, b.shape))
-        scale = (bool(a.max() > 1), bool(b.max() > 1))
-        if a.ndim == 3:
-            a, b = a[None], b[None]
-        h, w = a.shape[1:3]
-        nh, nw = self.get_padded_image_size(h, w, divisor)
-        info = None
-        if (nh, nw) != (h, w):
-            info = a.shape
-            pad = [(0, 0), (0, nh - h), (0, nw - w), (0, 0)]
-            a, b = np.pad(a, pad), np.pad(b, pad)
+            raise _shapes_differ(a.shape, b.shape)
+        scale = (_exceeds_one(a), _exceeds_one(b))
+        (a, b), info = self._batch_and_pad((a, b), divisor)
         return np.ascontiguousarray(a), np.ascontiguousarray(b), info, scale
 
     def adapt_x_matches(self, input_a, matches_a, sparse_flow, divisor=64):
         """adapt_x for (image, match mask, sparse flow) (net.py:324-392): image and mask to [0,1] when their max
         exceeds 1, mask gets its channel axis, all three batched and zero-padded to multiples of `divisor`."""
-        a = np.asarray(input_a)
-        a = a / 255.0 if a.max() > 1.0 else a.astype(np.float64)
-        m = np.asarray(matches_a)[..., np.newaxis]
-        m = m / 255.0 if m.max() > 1.0 else m.astype(np.float64)
+        a = _unit_range(input_a)
+        m = _unit_range(np.asarray(matches_a)[..., np.newaxis])
         sf = np.asarray(sparse_flow, np.float32)
-        assert m.shape[:2] == a.shape[:2] and m.shape[2] == 1, (
-            "Mask has invalid dimensions. Should be ({0}, {1}, 1) but are {2}".format(a.shape[0], a.shape[1], m.shape))
-        a, m, sf = a[None], m[None], sf[None]
-        h, w = a.shape[1:3]
-        nh, nw = self.get_padded_image_size(h, w, divisor)
-        info = None
-        if (nh, nw) != (h, w):
-            info = a.shape
-            pad = [(0, 0), (0, nh - h), (0, nw - w), (0, 0)]
-            a, m, sf = np.pad(a, pad), np.pad(m, pad), np.pad(sf, pad)
+        _check_mask(a, m)
+        (a, m, sf), info = self._batch_and_pad((a, m, sf), divisor)
         return a.astype(np.float32), m.astype(np.float32), sf.astype(np.float32), info
 
     def adapt_x_matches_u8(self, image, mask, sparse_flow, divisor=64):
@@ -195,18 +164,27 @@ class Net(object):
             raise ValueError("adapt_x_matches_u8 takes a uint8 image and a uint8 mask")
         m = m[..., np.newaxis]
         sf = np.asarray(sparse_flow, np.float32)
-        assert m.shape[:2] == a.shape[:2] and m.shape[2] == 1, (
-            "Mask has invalid dimensions. Should be ({0}, {1}, 1) but are {2}".format(a.shape[0], a.shape[1], m.shape))
-        scale = (bool(a.max() > 1), bool(m.max() > 1))
-        a, m, sf = a[None], m[None], sf[None]
-        h, w = a.shape[1:3]
-        nh, nw = self.get_padded_image_size(h, w, divisor)
-        info = None
-        if (nh, nw) != (h, w):
-            info = a.shape
-            pad = [(0, 0), (0, nh - h), (0, nw - w), (0, 0)]
-            a, m, sf = np.pad(a, pad), np.pad(m, pad), np.pad(sf, pad)
+        _check_mask(a, m)
+        scale = (_exceeds_one(a), _exceeds_one(m))
+        (a, m, sf), info = self._batch_and_pad((a, m, sf), divisor)
         return np.ascontiguousarray(a), np.ascontiguousarray(m), np.ascontiguousarray(sf), info, scale
+
+    def _batch_and_pad(self, arrays, divisor):
+        """The batch axis where it is missing, then every array zero-padded (bottom / right) to the multiples of
+        `divisor` above the first one's height and width.  Returns (arrays, shape of the batched first array) -- or
+        (arrays, None) when nothing had to be padded."""
+        arrays = [x[None] if x.ndim == 3 else x for x in arrays]
+        h, w = arrays[0].shape[1:3]
+        nh, nw = self.get_padded_image_size(h, w, divisor)
+        if (nh, nw) == (h, w):
+            return arrays, None
+        pad = [(0, 0), (0, nh - h), (0, nw - w), (0, 0)]
+        return [np.pad(x, pad) for x in arrays], arrays[0].shape
+
+    @staticmethod
+    def _original_size(padded, info):
+        """(h, w) of a frame before padding, from what its adaptor returned: `info`, or None where nothing was padded."""
+        return (info[-3], info[-2]) if info is not None else tuple(padded.shape[1:3])
 
     def postproc_y_hat_test(self, pred_flows, adapt_info=None):
         if adapt_info is not None:
@@ -218,82 +196,50 @@ class Net(object):
              out_path='./', input_type='image_pairs', save_image=True, save_flo=True, compute_metrics=True,
              gt_flow=None, new_par_folder=None, occlusions=False, occ_mask=None, inv_mask=None,
              variational_refinement=False):
-        """net.py:484-628.  input_type 'image_matches' (FlowNetS_interp): first image + match mask + sparse flow; with a
-        ground truth it prints the MPI-Sintel metrics block (net.py:612-625; `occ_mask` / `inv_mask`: paths of the
-        occlusion and invalid-pixel masks that split it into matched / unmatched regions).
-        `variational_refinement` (with `input_b_path`): the cropped flow is refined on the device by the EpicFlow
-        energy minimisation (src/variational.py, the reference's defaults) before metrics and outputs, as
-        net.py:578-589 does through its external binary.
-        `occlusions` ('image_pairs' only): the pair runs in both directions in one launch and the forward-backward check
-        (src/occlusion.py) writes `<name>_occ.png`, `<name>_occ_bw.png` (0 / 255) and `<name>_flow_bw.flo` next to the usual
-        outputs; the masks are kept in `self.last_occlusions`.  The return value stays the forward flow."""
+        """net.py:484-628: one pair, or one 'image_matches' set (FlowNetS_interp: first image + match mask + sparse flow),
+        as the one-line case of test_batch -- the same launchers with `batch_size` 1 (2 with `occlusions`), so
+        `variational_refinement` and `occlusions` mean what they mean there; refinement needs `input_b_path`.
+        What differs is what the reference's `test` does differently: the output folder and name (below), and the
+        metrics of a ground truth, printed -- the MPI-Sintel block (net.py:612-625) for 'image_matches' or with
+        `occ_mask` / `inv_mask` (paths of the masks that split it into matched / unmatched regions), else one
+        `EPE all` line.  Returns the forward flow."""
         if occlusions and input_type == 'image_matches':
             raise ValueError("occlusions need the second frame as a network input: input_type 'image_matches' has no "
                              "matches for it")
         if self.weights is None:
             self.load_weights(checkpoint)
+        occ_files = None
         if input_type == 'image_matches':
             if matches_a_path is None or sparse_flow_path is None:
                 raise ValueError("input_type 'image_matches' needs matches_a_path and sparse_flow_path")
-            img, mask, sparse = imread(input_a_path), imread_gray(matches_a_path), read_flow(sparse_flow_path)
-            if img.dtype == np.uint8 and mask.dtype == np.uint8:
-                # the files' bytes cross the host link as they are; `/ 255.0`, `* 0.05` and the concat run on the device
-                a, m, sf, info, scale = self.adapt_x_matches_u8(img, mask, sparse)
-                inputs = {'input_a': a, 'matches_a': m, 'sparse_flow': sf, 'scale': [scale]}
-            else:
-                a, m, sf, info = self.adapt_x_matches(img, mask, sparse)
-                inputs = {'input_a': a, 'matches_a': m, 'sparse_flow': sf}
-            preds = self.model(inputs, LONG_SCHEDULE, trainable=False)
+            fields = dict(matches_line_fields([input_a_path, matches_a_path, sparse_flow_path]), image_b=input_b_path)
+            flow = self._infer_matches([fields], 1, variational_refinement)[0]
         elif occlusions:
-            # both directions in the two slots of one launch; the forward flow is refined after the masks are formed
             flow, flow_bw, occ_fw, occ_bw = self._infer_pairs([[input_a_path, input_b_path]], 2, variational_refinement,
                                                               bidirectional=True)[0]
             self.last_occlusions = [(occ_fw, occ_bw)]
-            preds = info = None  # cropped (and refined) already
+            occ_files = (flow_bw, occ_fw, occ_bw)
         else:
-            # image files decode to uint8: they cross the host link as bytes and are normalised on the device
-            a, b, info, scale = self.adapt_x_u8(imread(input_a_path), imread(input_b_path))
-            preds = self.model({'input_a': a, 'input_b': b, 'scale': scale}, LONG_SCHEDULE, trainable=False)
-        y_info = (info[-3], info[-2], 2) if info is not None else None
-        if preds is None:
-            pass
-        elif variational_refinement and input_b_path is not None:
-            from .variational import refine
-            pred = self.postproc_y_hat_test(preds['flow'][0].float(), y_info)
-            dev = pred.device
-            fa = torch.from_numpy(np.ascontiguousarray(imread(input_a_path))).to(dev)
-            fb = torch.from_numpy(np.ascontiguousarray(imread(input_b_path))).to(dev)
-            flow = refine(pred, fa, fb).cpu().numpy()
-        else:
-            flow = preds['flow'][0].float().cpu().numpy()
-            flow = self.postproc_y_hat_test(flow, y_info)
+            flow = self._infer_pairs([[input_a_path, input_b_path]], 1, variational_refinement)[0]
 
+        # net.py:546-547: the folder is the name of the first image's directory (_write_line: `split('/')[-2]`)
         parent = new_par_folder if new_par_folder is not None else \
             os.path.basename(os.path.dirname(os.path.abspath(input_a_path)))
+        # net.py:546: `splitext`, an extension of any length (_write_line: `[:-4]`)
         unique_name = os.path.splitext(os.path.basename(input_a_path))[0]
-        out_dir = os.path.join(out_path, parent)
         max_flow = -1
         gt = None
         if compute_metrics and gt_flow is not None:
             gt = read_flow(gt_flow)
+            # net.py:595: the largest motion of the ground truth (_write_line: its largest component)
             max_flow = float(np.max(np.sqrt(gt[:, :, 0] ** 2 + gt[:, :, 1] ** 2)))
-        if save_image or save_flo:
-            os.makedirs(out_dir, exist_ok=True)
-        if save_image:
-            full = os.path.join(out_dir, unique_name + '_viz.png')
-            imsave(full, flow_to_image(flow.copy()))
-            imsave(full.replace('.png', '_norm_gt_max_motion.png'), flow_to_image(flow.copy(), maxflow=max_flow))
-        if save_flo:
-            write_flow(flow, os.path.join(out_dir, unique_name + '_flow.flo'))
-        if occlusions:
-            self._write_occlusions(out_dir, unique_name, flow_bw, occ_fw, occ_bw)
+        self._write_outputs(flow, os.path.join(out_path, parent), unique_name, max_flow, save_image, save_flo, occ_files)
         if gt is not None and (input_type == 'image_matches' or occ_mask is not None or inv_mask is not None):
             occ = imread_gray(occ_mask) if occ_mask is not None else None
             inv = imread_gray(inv_mask) if inv_mask is not None else None
             metrics = compute_all_metrics(flow, gt, occ_mask=occ, inv_mask=inv)[0]
             print(get_metrics(metrics, flow_fname=unique_name))
         elif gt is not None:
-            from .flowlib import endpoint_error
             print("{}: EPE all = {:.4f}".format(unique_name, endpoint_error(flow, gt)))
         return flow
 
@@ -310,21 +256,21 @@ class Net(object):
         one of the layouts of `matches_line_fields` -- `I1 MM SF [GT [[OCC [INV]] I2]]`: the last field of a 5-, 6- or
         7-field line is the second image; the reference's `I1 MM SF GT OCC` and `I1 MM SF GT OCC INV` branches are
         shadowed by those (net.py:773 / :798, :809 / :820) and are unreachable here as well.
-        Outputs per line as Net.test writes them; with a ground truth, the MPI-Sintel metrics block goes to
-        `<list name>_metrics.log` (or stdout), and `accumulate_metrics` appends the sequence averages.
+        Per line: `<name>_viz.png`, `<name>_viz_norm_gt_max_motion.png` and `<name>_flow.flo` (_write_outputs); with a
+        ground truth, the MPI-Sintel metrics block goes to `<list name>_metrics.log` (or stdout), and
+        `accumulate_metrics` appends the sequence averages.
         `width`/`height` are kept for signature compatibility (the reference sizes its placeholders with them); frames
         are padded by their own size.  `batch_size` lines of equal padded size go through the engine per launch (the
-        reference feeds one per sess.run).  `variational_refinement` refines the cropped flows of each group of
-        equally sized frames in one device call (src/variational.py; the reference runs its binary per line,
-        net.py:889-901); an 'image_matches' line without a second image comes back unrefined.
+        reference feeds one per sess.run).  `variational_refinement`: the cropped flows are refined on the device by
+        the EpicFlow energy minimisation (src/variational.py, the reference's defaults; the reference runs its binary
+        per line, net.py:889-901) before metrics and outputs; an 'image_matches' line without a second image comes
+        back unrefined.
         `occlusions` / `occlusions_for_metrics` ('image_pairs' only, `batch_size` even): every line runs in both
-        directions -- (a, b) in slot 2k and (b, a) in slot 2k + 1 of the same `batch_size` engine, so `batch_size // 2`
-        lines per launch -- and the forward-backward check (src/occlusion.py) gives an occlusion mask per direction, kept
-        as `self.last_occlusions` [(occ_fw, occ_bw) uint8 0 / 255 per line].  With `occlusions` a line also writes
-        `<name>_occ.png`, `<name>_occ_bw.png` and `<name>_flow_bw.flo`; with `occlusions_for_metrics` a line with a ground
-        truth and no occlusion mask file takes the estimated forward mask for the matched / unmatched split of its
-        metrics.  The return value stays the forward flows; with `variational_refinement` only those are refined, after
-        the masks are formed."""
+        directions, `batch_size // 2` lines per launch (_infer_bidirectional), and the forward-backward check gives an
+        occlusion mask per direction, kept as `self.last_occlusions` [(occ_fw, occ_bw) uint8 0 / 255 per line].  With
+        `occlusions` a line also writes `<name>_occ.png`, `<name>_occ_bw.png` and `<name>_flow_bw.flo`; with
+        `occlusions_for_metrics` a line with a ground truth and no occlusion mask file takes the estimated forward mask
+        for the matched / unmatched split of its metrics.  Returns the forward flows."""
         if input_type not in ('image_pairs', 'image_matches'):
             raise NotImplementedError("test_batch: input_type must be 'image_pairs' or 'image_matches', got %r" % (input_type,))
         bidirectional = bool(occlusions or occlusions_for_metrics)
@@ -345,7 +291,6 @@ class Net(object):
             os.makedirs(os.path.dirname(full) or '.', exist_ok=True)
             logfile = open(full, 'w')
             if new_par_folder is not None:
-                import datetime
                 logfile.write("Today is {}\nOpening and logging experiment '{}'\n Written to file: '{}'\n".format(
                     datetime.datetime.now().strftime('%d-%m-%y_%H-%M-%S'), new_par_folder, full))
         rows, counts = [], np.zeros(4, np.int64)  # not occluded / empty S0-10 / S10-40 / S40+ frame counts
@@ -385,7 +330,6 @@ class Net(object):
             if accumulate_metrics and rows:
                 avg = self._average_metrics(np.array(rows, np.float64).reshape(len(rows), -1), counts)
                 if logfile is not None:
-                    import datetime
                     logfile.write('\n\nToday is: {}\nNow logging final averaged metrics \n\n'.format(
                         datetime.datetime.now().strftime('%d-%m-%y_%H-%M-%S')))
                     logfile.write(get_metrics(dict(zip(self._METRIC_ORDER, avg)), average=True))
@@ -397,29 +341,20 @@ class Net(object):
 
     def _write_line(self, flow, first_path, gt_path, occ_path, inv_path, out_path, new_par_folder, save_image, save_flo,
                     compute_metrics, logfile, occlusions=None, estimated_occ=None):
-        """What test_batch leaves behind for one list line, whatever its input type: the two PNGs, the .flo and -- with
-        a ground truth -- the metrics block (to `logfile`, or stdout).  `occlusions` (flow_bw, occ_fw, occ_bw): the
-        files of _write_occlusions as well.  `estimated_occ`: the occlusion mask of a line that names no mask file.
-        Returns (metrics, flags) of compute_all_metrics, or (None, None)."""
+        """What test_batch leaves behind for one list line, whatever its input type: the files of _write_outputs and --
+        with a ground truth -- the metrics block (to `logfile`, or stdout).  `estimated_occ`: the occlusion mask of a
+        line that names no mask file.  Returns (metrics, flags) of compute_all_metrics, or (None, None)."""
         gt = read_flow(gt_path) if gt_path is not None else None
         occ = imread_gray(occ_path) if occ_path is not None and compute_metrics else None
         if occ is None and occ_path is None and compute_metrics:
             occ = estimated_occ
         inv = imread_gray(inv_path) if inv_path is not None and compute_metrics else None
+        # net.py:909-910: the largest component of the ground truth (test: its largest motion)
         max_flow = np.max(gt) if (compute_metrics and gt is not None) else -1
+        # net.py:853: the second-last component of the path as the list spells it (test: the directory's name)
         parent = first_path.split('/')[-2] if new_par_folder is None else new_par_folder
-        unique_name = os.path.basename(first_path)[:-4]
-        out_dir = os.path.join(out_path, parent)
-        if save_image or save_flo:
-            os.makedirs(out_dir, exist_ok=True)
-        if save_image:
-            full = os.path.join(out_dir, unique_name + '_viz.png')
-            imsave(full, flow_to_image(flow.copy()))
-            imsave(full.replace('.png', '_norm_gt_max_motion.png'), flow_to_image(flow.copy(), maxflow=max_flow))
-        if save_flo:
-            write_flow(flow, os.path.join(out_dir, unique_name + '_flow.flo'))
-        if occlusions is not None:
-            self._write_occlusions(out_dir, unique_name, *occlusions)
+        unique_name = os.path.basename(first_path)[:-4]  # a three-letter extension (test: `splitext`)
+        self._write_outputs(flow, os.path.join(out_path, parent), unique_name, max_flow, save_image, save_flo, occlusions)
         if not (compute_metrics and gt is not None):
             return None, None
         m, *flags = compute_all_metrics(flow, gt, occ_mask=occ, inv_mask=inv)
@@ -430,43 +365,80 @@ class Net(object):
             print(text)
         return m, flags
 
+    @staticmethod
+    def _write_outputs(flow, out_dir, unique_name, max_flow, save_image, save_flo, occlusions=None):
+        """`<name>_viz.png`, `<name>_viz_norm_gt_max_motion.png` (colours scaled to `max_flow`) and `<name>_flow.flo` under
+        `out_dir`; with `occlusions` (flow_bw, occ_fw, occ_bw) also `<name>_occ.png` (forward mask, 0 / 255),
+        `<name>_occ_bw.png` and `<name>_flow_bw.flo`."""
+        stem = os.path.join(out_dir, unique_name)
+        if save_image or save_flo or occlusions is not None:
+            os.makedirs(out_dir, exist_ok=True)
+        if save_image:
+            imsave(stem + '_viz.png', flow_to_image(flow.copy()))
+            imsave(stem + '_viz_norm_gt_max_motion.png', flow_to_image(flow.copy(), maxflow=max_flow))
+        if save_flo:
+            write_flow(flow, stem + '_flow.flo')
+        if occlusions is not None:
+            flow_bw, occ_fw, occ_bw = occlusions
+            imsave(stem + '_occ.png', occ_fw)
+            imsave(stem + '_occ_bw.png', occ_bw)
+            write_flow(flow_bw, stem + '_flow_bw.flo')
+
+    # ---- the launchers: list lines -> cropped flows ------------------------------------------------------
+    def _launch_groups(self, samples, keys, batch_size, interp=False):
+        """One engine launch per group of lines with equal `keys[i]`: (padded frame shape,) for the uint8 interp engine
+        (`interp`), (padded frame shape, scale) for the uint8 pair engine, whose input buffers take one normalisation
+        decision per launch.  samples[i]: the input tuples line i puts into neighbouring slots of the `batch_size`
+        engine; a short group leaves zero samples behind it, so that one engine serves the whole list.
+        Yields (engine, line indices, batch arrays, key) after each launch."""
+        groups = {}
+        for i, key in enumerate(keys):
+            groups.setdefault(key, []).append(i)
+        for key, idxs in groups.items():
+            slots = [sample for i in idxs for sample in samples[i]]
+            arrays = [np.zeros((batch_size,) + x.shape, x.dtype) for x in slots[0]]
+            for j, sample in enumerate(slots):
+                for dst, src in zip(arrays, sample):
+                    dst[j] = src
+            height, width = key[0][1:3]
+            if interp:
+                eng = self.engine(batch_size, height, width, interp_u8_inputs=True)
+                eng.set_inputs_interp_u8(*arrays)
+            else:
+                eng = self.engine(batch_size, height, width, uint8_inputs=True)
+                eng.set_inputs_u8(*arrays, key[1])
+            eng.launch()
+            yield eng, idxs, arrays, key
+
     def _infer_pairs(self, chunk, batch_size, variational_refinement=False, bidirectional=False):
-        """Flows (cropped to each frame's size) of up to `batch_size` list lines, one engine launch per group of
-        equally sized frames; a short group is padded with zero pairs so that one engine serves the whole list.
+        """Flows (cropped to each frame's size) of up to `batch_size` list lines (_launch_groups).
         With `variational_refinement`, one refinement call per group of equal original size.
         `bidirectional`: up to `batch_size // 2` lines, see _infer_bidirectional."""
         if bidirectional:
             return self._infer_bidirectional(chunk, batch_size, variational_refinement)
         frames = [self.adapt_x_u8(imread(p[0]), imread(p[1])) for p in chunk]
         out = [None] * len(chunk)
-        by_shape = {}
-        for i, (a, _, _, scale) in enumerate(frames):
-            by_shape.setdefault((a.shape, scale), []).append(i)  # one normalisation decision per launch
-        for (shape, scale), idxs in by_shape.items():
-            n = batch_size
-            a = np.zeros((n,) + shape[1:], np.uint8)
-            b = np.zeros_like(a)
-            for j, i in enumerate(idxs):
-                a[j], b[j] = frames[i][0][0], frames[i][1][0]
-            eng = self.engine(n, shape[1], shape[2], uint8_inputs=True)
-            eng.set_inputs_u8(a, b, scale)
-            eng.launch()
+        for eng, idxs, _, _ in self._launch_groups([[(a[0], b[0])] for a, b, _, _ in frames],
+                                                   [(a.shape, scale) for a, _, _, scale in frames], batch_size):
             if variational_refinement:
                 self._refine_group(eng.outputs['flow'], frames, idxs, out)
                 continue
             pred = eng.outputs['flow'].float().cpu().numpy()
             for j, i in enumerate(idxs):
-                info = frames[i][2]
-                out[i] = self.postproc_y_hat_test(pred[j], (info[-3], info[-2], 2) if info is not None else None).copy()
+                out[i] = self._crop(pred[j], frames[i][0], frames[i][2])
         return out
+
+    def _crop(self, pred, padded, info):
+        """The [h,w,2] part of a padded host flow that belongs to the frame, as an array of its own."""
+        return self.postproc_y_hat_test(pred, self._original_size(padded, info) + (2,)).copy()
 
     def _infer_bidirectional(self, chunk, batch_size, variational_refinement=False):
         """(flow_fw, flow_bw, occ_fw, occ_bw) of up to `batch_size // 2` list lines: flows [h,w,2] float32 and
         forward-backward occlusion masks [h,w] uint8 0 / 255 (src/occlusion.py), cropped to each frame's size.  Line k
-        of a group of equally sized frames fills slot 2k with (a, b) and slot 2k + 1 with (b, a) of the `batch_size`
-        engine _infer_pairs uses: the backward flows ride on the launch that is running anyway.  Both flows are cropped
-        on the device and the check reads the crops in place, one call per run of neighbouring lines of equal
-        original size.  With `variational_refinement` the forward flow is refined, after the masks are formed."""
+        of a group fills slot 2k with (a, b) and slot 2k + 1 with (b, a) of the `batch_size` engine _infer_pairs uses:
+        the backward flows ride on the launch that is running anyway.  Both flows are cropped on the device and the
+        check reads the crops in place, one call per run of neighbouring lines of equal original size.  With
+        `variational_refinement` the forward flow is refined, after the masks are formed."""
         from .occlusion import occlusion
         if batch_size % 2:
             raise ValueError("bidirectional inference puts the two directions of a line into neighbouring slots: "
@@ -476,30 +448,17 @@ class Net(object):
                              % (batch_size // 2, len(chunk)))
         frames = [self.adapt_x_u8(imread(p[0]), imread(p[1])) for p in chunk]
         out = [None] * len(chunk)
-        by_shape = {}
-        for i, (a, _, _, scale) in enumerate(frames):
-            by_shape.setdefault((a.shape, scale), []).append(i)
-        for (shape, scale), idxs in by_shape.items():
-            a = np.zeros((batch_size,) + shape[1:], np.uint8)
-            b = np.zeros_like(a)
-            for k, i in enumerate(idxs):
-                a[2 * k], b[2 * k] = frames[i][0][0], frames[i][1][0]
-                a[2 * k + 1], b[2 * k + 1] = frames[i][1][0], frames[i][0][0]
-            eng = self.engine(batch_size, shape[1], shape[2], uint8_inputs=True)
-            eng.set_inputs_u8(a, b, scale)
-            eng.launch()
+        for eng, idxs, (a, b), (_, scale) in self._launch_groups([[(a[0], b[0]), (b[0], a[0])] for a, b, _, _ in frames],
+                                                                 [(a.shape, scale) for a, _, _, scale in frames], batch_size):
             flow = eng.outputs['flow'].float()
             if scale[0] != scale[1]:
-                # an input buffer has one normalisation decision per launch and the two frames disagree: the odd slots
-                # come from a second launch with the decisions swapped
+                # the two frames disagree on the launch's one decision per input buffer: the odd slots come from a
+                # second launch with the decisions swapped
                 flow = flow.clone()
                 eng.set_inputs_u8(a, b, scale[::-1])
                 eng.launch()
                 flow[1::2] = eng.outputs['flow'][1::2].float()
-            sizes = []
-            for i in idxs:
-                info = frames[i][2]
-                sizes.append((info[-3], info[-2]) if info is not None else tuple(shape[1:3]))
+            sizes = [self._original_size(frames[i][0], frames[i][2]) for i in idxs]
             k = 0
             while k < len(idxs):
                 m = 1
@@ -521,36 +480,16 @@ class Net(object):
                     out[i] = (refined[i],) + out[i][1:]
         return out
 
-    @staticmethod
-    def _write_occlusions(out_dir, unique_name, flow_bw, occ_fw, occ_bw):
-        """`<name>_occ.png` (forward mask, 0 / 255), `<name>_occ_bw.png` and `<name>_flow_bw.flo`."""
-        os.makedirs(out_dir, exist_ok=True)
-        imsave(os.path.join(out_dir, unique_name + '_occ.png'), occ_fw)
-        imsave(os.path.join(out_dir, unique_name + '_occ_bw.png'), occ_bw)
-        write_flow(flow_bw, os.path.join(out_dir, unique_name + '_flow_bw.flo'))
-
     def _infer_matches(self, fields, batch_size, variational_refinement=False):
         """_infer_pairs for 'image_matches' lines (`fields`: matches_line_fields records): image, match mask and sparse
-        flow of up to `batch_size` lines of equal padded size through one launch of the uint8 interp engine.  The scale
-        decisions travel per sample (Engine.in_flags), so lines with 0/255 and 0/1 masks share a launch.  With
-        `variational_refinement`, the lines that name a second image are refined on (I1, I2); the others are not."""
+        flow through the uint8 interp engine.  The scale decisions travel per sample (Engine.in_flags), so lines with
+        0/255 and 0/1 masks share a launch.  With `variational_refinement`, the lines that name a second image are
+        refined on (I1, I2); the others are not."""
         frames = [self.adapt_x_matches_u8(imread(f['image']), imread_gray(f['matches']), read_flow(f['sparse']))
                   for f in fields]
         out = [None] * len(fields)
-        by_shape = {}
-        for i, fr in enumerate(frames):
-            by_shape.setdefault(fr[0].shape, []).append(i)
-        for shape, idxs in by_shape.items():
-            n = batch_size
-            a = np.zeros((n,) + shape[1:], np.uint8)
-            m = np.zeros((n,) + shape[1:3], np.uint8)
-            sf = np.zeros((n,) + shape[1:3] + (2,), np.float32)
-            flags = np.zeros((n, 2), np.uint8)
-            for j, i in enumerate(idxs):
-                a[j], m[j], sf[j], flags[j] = frames[i][0][0], frames[i][1][0, :, :, 0], frames[i][2][0], frames[i][4]
-            eng = self.engine(n, shape[1], shape[2], interp_u8_inputs=True)
-            eng.set_inputs_interp_u8(a, m, sf, flags)
-            eng.launch()
+        samples = [[(a[0], m[0, :, :, 0], sf[0], np.array(scale, np.uint8))] for a, m, sf, _, scale in frames]
+        for eng, idxs, _, _ in self._launch_groups(samples, [(fr[0].shape,) for fr in frames], batch_size, interp=True):
             slots = [j for j, i in enumerate(idxs) if variational_refinement and fields[i]['image_b'] is not None]
             if slots:
                 # (padded first frame, padded second frame, info) per line: the records _refine_group reads
@@ -563,8 +502,7 @@ class Net(object):
                 pred = eng.outputs['flow'].float().cpu().numpy()
                 for j, i in enumerate(idxs):
                     if j not in slots:
-                        info = frames[i][3]
-                        out[i] = self.postproc_y_hat_test(pred[j], (info[-3], info[-2], 2) if info is not None else None).copy()
+                        out[i] = self._crop(pred[j], frames[i][0], frames[i][3])
         return out
 
     @staticmethod
@@ -572,20 +510,17 @@ class Net(object):
         """uint8 frame [H,W,3] zero-padded (bottom / right) to the [1,Hp,Wp,3] shape of `padded`."""
         img = np.asarray(image)
         if img.shape[0] > padded.shape[1] or img.shape[1] > padded.shape[2]:
-            raise AssertionError("FATAL: image dimensions do not match. Image 1 has shape: {0}, "
-                                 "Image 2 has shape: {1}".format(padded.shape, img.shape))
+            raise _shapes_differ(padded.shape, img.shape)
         return np.pad(img, [(0, padded.shape[1] - img.shape[0]), (0, padded.shape[2] - img.shape[1]), (0, 0)])[None]
 
     @staticmethod
     def _refine_group(pred, frames, idxs, out):
-        """Variational refinement of the cropped flows pred[j] of frames[idxs[j]], one call per original size; the
-        frames are read in place from their padded device copies."""
+        """Variational refinement of the cropped flows pred[j] of frames[idxs[j]] = (padded first frame, padded second
+        frame, info, ...), one call per original size; the frames are read in place from their padded device copies."""
         from .variational import refine
         by_size = {}
         for j, i in enumerate(idxs):
-            info = frames[i][2]
-            size = (info[-3], info[-2]) if info is not None else tuple(frames[i][0].shape[1:3])
-            by_size.setdefault(size, []).append((j, i))
+            by_size.setdefault(Net._original_size(frames[i][0], frames[i][2]), []).append((j, i))
         for (h, w), members in by_size.items():
             js = torch.tensor([j for j, _ in members], device=pred.device)
             flow = pred.float().index_select(0, js)[:, :h, :w]
@@ -652,6 +587,26 @@ def str2bool(v):
     if v.lower() in ('no', 'false', 'f', 'n', '0'):
         return False
     raise argparse.ArgumentTypeError('Boolean value expected.')
+
+
+def _exceeds_one(x):
+    """adapt_x's decision (net.py:334-345): an input whose maximum exceeds 1 holds [0,255] and is divided by 255."""
+    return bool(x.max() > 1)
+
+
+def _unit_range(x):
+    x = np.asarray(x)
+    return x / 255.0 if _exceeds_one(x) else x.astype(np.float64)
+
+
+def _shapes_differ(shape_a, shape_b):
+    return AssertionError("FATAL: image dimensions do not match. Image 1 has shape: {0}, "
+                          "Image 2 has shape: {1}".format(shape_a, shape_b))
+
+
+def _check_mask(image, mask):
+    assert mask.shape[:2] == image.shape[:2] and mask.shape[2] == 1, (
+        "Mask has invalid dimensions. Should be ({0}, {1}, 1) but are {2}".format(image.shape[0], image.shape[1], mask.shape))
 
 
 def _is_u8(x):

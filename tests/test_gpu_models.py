@@ -575,3 +575,55 @@ def test_flow_resize_inside_the_consuming_op(model, shape, monkeypatch):
     assert len(flows) >= nsub
     for k in flows:     # the sub-networks' full-resolution flows are still there, written by their consumers
         assert torch.equal(eng.bufs[k], base.bufs[k]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("refined", [False, True])
+@pytest.mark.parametrize("input_type", ["image_pairs", "image_matches"])
+def test_single_run_equals_the_one_line_list(input_type, refined, tmp_path):
+    """Net.test is the one-line case of Net.test_batch: one 70 x 100 pair (FlowNetS) or match set (FlowNetS_interp), which
+    pads to 128 x 128, gives byte-identical flows and `.flo` files both ways -- plain, and with the variational refinement
+    reading frames and flow in place from their padded buffers (for matches: a 5-field line, `I1 MM SF GT I2`)."""
+    from PIL import Image
+    from src import flowlib
+    from src.flownet_s.flownet_s import FlowNetS
+    from src.flownet_s_interp.flownet_s_interp import FlowNetS_interp
+    from src.net import Mode
+    h, w = 70, 100
+    rng = np.random.default_rng(31)
+    seq = tmp_path / "seq"
+    seq.mkdir()
+    a = rng.integers(0, 256, (h, w, 3)).astype(np.float32)
+    a = ((a + np.roll(a, 1, 0) + np.roll(a, 1, 1) + np.roll(a, (1, 1), (0, 1))) / 4).astype(np.uint8)
+    b = np.roll(a, (1, -2), (0, 1))
+    m = (rng.random((h, w)) > 0.9).astype(np.uint8) * 255
+    sf = np.broadcast_to(np.float32([-2, 1]), (h, w, 2)) * (m > 0)[..., None]
+    p = {k: str(seq / ("frame_0001" + s)) for k, s in (("a", ".png"), ("b", "_next.png"), ("m", "_mask.png"),
+                                                       ("sf", "_sparse.flo"), ("gt", "_gt.flo"))}
+    Image.fromarray(a).save(p["a"])
+    Image.fromarray(b).save(p["b"])
+    Image.fromarray(m).save(p["m"])
+    flowlib.write_flow(sf.astype(np.float32), p["sf"])
+    flowlib.write_flow(np.broadcast_to(np.float32([-2, 1]), (h, w, 2)).copy(), p["gt"])
+    if input_type == "image_pairs":
+        net = FlowNetS(mode=Mode.TEST, dtype="f16x2")
+        line, single_kw = [p["a"], p["b"]], {}
+    else:
+        net = FlowNetS_interp(mode=Mode.TEST, dtype="f16x2")
+        line = [p["a"], p["m"], p["sf"]] + ([p["gt"], p["b"]] if refined else [])
+        single_kw = dict(matches_a_path=p["m"], sparse_flow_path=p["sf"])
+    net.load_weights(None, seed=1234)
+    lst = tmp_path / "one.txt"
+    lst.write_text(" ".join(line) + "\n")
+    kw = dict(input_type=input_type, save_image=False, compute_metrics=False, variational_refinement=refined)
+    single = net.test(None, p["a"], input_b_path=p["b"], out_path=str(tmp_path / "single"), **single_kw, **kw)
+    listed = net.test_batch(None, str(lst), str(tmp_path / "list"), batch_size=1, log_metrics2file=False, **kw)
+    assert len(listed) == 1 and single.shape == (h, w, 2) and single.dtype == np.float32 and np.isfinite(single).all()
+    assert single.tobytes() == listed[0].tobytes()
+    flo = (tmp_path / "single" / "seq" / "frame_0001_flow.flo").read_bytes()
+    assert flo == (tmp_path / "list" / "seq" / "frame_0001_flow.flo").read_bytes()
+    assert np.array_equal(flowlib.read_flow(str(tmp_path / "single" / "seq" / "frame_0001_flow.flo")), single)
+    if refined:
+        plain = net.test(None, p["a"], input_b_path=p["b"], out_path=str(tmp_path / "plain"), save_flo=False, **single_kw,
+                         **dict(kw, variational_refinement=False))
+        assert not np.array_equal(plain, single)                  # the refinement did run
