@@ -75,6 +75,9 @@ PROTOTYPES = {
     "fn2_conv2d_splits": (_i, [C.POINTER(Fn2ConvDesc)]),
     "fn2_augment_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "fn2_flow_augmentation_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "fn2_selflow_workspace_bytes": (C.c_int64, [_i, _i, _i]),
+    "fn2_selflow_stats": (_i, [_p, _p, _p, _p, _p, C.c_int64, _i, _i, _i, _p]),
+    "fn2_selflow_apply": (_i, [_p] * 15 + [C.c_int64, _i, _i, _i, _p]),
     "fn2_flow_head_gather": (_i, [_p, _i, _p, _p, _i, _i, _i, _p]),
     "fn2_upsample_flow": (_i, [_p, _p, _p, _tp, _i, _i, _i, _p]),
     "fn2_flow_head_tail": (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _tp, _p]),

@@ -3,6 +3,8 @@ over two sample sources: the reference's ZLIB TFRecord files (src/tfrecord.py re
 text file listing `image_a image_b flow.flo` per line (the triples the TFRecords were built from); samples are
 batched on the host, and the augmentation runs on the GPU through the preprocessing plugin's op surface (src/preprocessing.py):
 DataAugmentation on both images (image b inherits image a's transform), FlowAugmentation on the ground truth.
+The SelFlow-style augmentation the reference's loader itself applies (dataloader.py:35-113) is src/data_augmentation.py:
+`load_interp_batches(data_augmentation=True)` and `load_batches(augmentation='selflow')` switch it on.
 
 PREPROCESS values are the reference's FlyingChairs configuration (dataset_configs.py:60-157) as data.
 """
@@ -95,12 +97,17 @@ def is_tfrecord(path):
 
 
 def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, data_augmentation=True, seed=0,
-                 global_step=0, epochs=None, image_size=(384, 512), shuffle_buffer=256):
+                 global_step=0, epochs=None, image_size=(384, 512), shuffle_buffer=256, augmentation="plugin",
+                 fast_mode=False):
     """Generator of (image_a, image_b, flow) device tensors [B,h,w,3|3|2]; images in [0,1].  ``list_path`` is a
     text file of `image_a image_b flow.flo` triples or a ``.tfrecords`` file as the reference's converter writes it
     (``image_size`` = the dataset's PADDED_IMAGE_HEIGHT/WIDTH, dataset_configs.py:42-43).  With data_augmentation
     the crop is (crop_height, crop_width) and the flow is transformed with the two augmentation matrices
-    (dataloader.py:480-540); without it the samples pass through unchanged."""
+    (dataloader.py:480-540); without it the samples pass through unchanged.  ``augmentation='selflow'`` takes the
+    augmentation the reference's live loader applies to image pairs instead of the plugin's (augment_all_estimation,
+    dataloader.py:93-113 -> src/data_augmentation.py): flips, a channel permutation and a colour chain per image, no crop."""
+    if augmentation not in ("plugin", "selflow"):
+        raise ValueError("augmentation must be 'plugin' or 'selflow', got %r" % (augmentation,))
     rng = np.random.default_rng(seed)
     rows = None if is_tfrecord(list_path) else read_list(list_path)
     a_cfg, b_cfg = config_to_arrays(preprocess["image_a"]), config_to_arrays(preprocess["image_b"])
@@ -121,6 +128,9 @@ def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, dat
             if not data_augmentation:
                 dev = lambda x: torch.from_numpy(x).to(P._hip.require_device())
                 yield dev(a), dev(b), dev(f)
+            elif augmentation == "selflow":
+                from . import data_augmentation as DA
+                yield DA.augment_all_estimation(a, b, f, params=DA.draw_estimation_params(rng, len(a), fast_mode=fast_mode))
             else:
                 oa, ob, ta, itb = P.data_augmentation(
                     a, b, step, crop, a_cfg["name"], a_cfg["rand_type"], a_cfg["exp"], a_cfg["mean"], a_cfg["spread"],
@@ -141,15 +151,22 @@ def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, dat
 
 
 def load_interp_batches(tfrecord_path, batch_size, image_size=(384, 512), seed=0, epochs=None, scale=False,
-                        shuffle_buffer=256):
+                        shuffle_buffer=256, data_augmentation=False, split="train", invalid_like=-1, num_distrib=2,
+                        min_val=0, ff_like=-1):
     """Batches for FlowNetS_interp from the reference's `image_matches` records (dataloader.py:211-245: image_a and
     matches_a float64, sparse_flow / edges_a / flow float32, all at the dataset's padded size): device tensors
-    (image_a [B,h,w,3], matches_a [B,h,w,1], sparse_flow [B,h,w,2], edges_a [B,h,w,1], flow [B,h,w,2]).  No
-    augmentation: the reference's `augment_all_interp` (random crops / flips / colour / re-sampling of the sparse
-    flow, dataloader.py:30-80) is not built."""
+    (image_a [B,h,w,3], matches_a [B,h,w,1], sparse_flow [B,h,w,2], edges_a [B,h,w,1], flow [B,h,w,2]).
+    With ``data_augmentation`` every batch goes through the reference's `augment_all_interp` (dataloader.py:35-80:
+    re-sampling of the matches and the sparse flow, flips, channel permutation, colour chain) on the GPU
+    (src/data_augmentation.py), or with ``split='valid'`` through `augment_all_interp_validation` (:83-90: re-sampling
+    only), as dataloader.py:478-499 chooses; the decisions are drawn per sample from a stream of their own seeded by
+    ``seed``, so the order of the samples does not depend on the switch.  Off (the default), the records pass through."""
     from . import tfrecord
+    if split not in ("train", "valid"):
+        raise ValueError("split must be 'train' or 'valid', got %r" % (split,))
     names = ("image_a", "matches_a", "sparse_flow", "edges_a", "flow")
     rng = np.random.default_rng(seed)
+    aug_rng = np.random.default_rng([int(seed), 0x5E1F]) if data_augmentation else None
     div = 255.0 if scale else 1.0
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(P._hip.require_device())
     epoch = 0
@@ -157,7 +174,16 @@ def load_interp_batches(tfrecord_path, batch_size, image_size=(384, 512), seed=0
         buf, pick, produced = [], [], False
 
         def emit(items):
-            return tuple(dev(np.stack([it[i] for it in items]).astype(np.float32)) for i in range(5))
+            batch = tuple(dev(np.stack([it[i] for it in items]).astype(np.float32)) for i in range(5))
+            if not data_augmentation:
+                return batch
+            from . import data_augmentation as DA
+            n, h, w = batch[0].shape[:3]
+            if split == "train":
+                return DA.augment_all_interp(*batch, params=DA.draw_interp_params(
+                    aug_rng, n, h, w, invalid_like, num_distrib, min_val, ff_like))
+            return DA.augment_all_interp_validation(*batch, params=DA.draw_validation_params(
+                aug_rng, n, h, w, invalid_like, num_distrib, min_val, ff_like))
 
         def samples():
             for smp in tfrecord.read_samples(tfrecord_path, image_size[0], image_size[1], names):

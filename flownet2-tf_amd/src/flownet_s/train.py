@@ -80,7 +80,9 @@ def main(flags):
     model = getattr(flags, "model", "FlowNetS")
     wts = W.load_weights(flags.checkpoint) if flags.checkpoint else W.init_weights(model, flags.seed)
     pre = FLYING_CHAIRS_PREPROCESS
-    h, w = (pre["crop_height"], pre["crop_width"]) if flags.augment else (flags.height, flags.width)
+    augmentation = getattr(flags, "augmentation", "plugin")  # 'selflow' keeps the frame size: it has no crop
+    h, w = ((pre["crop_height"], pre["crop_width"]) if flags.augment and augmentation == "plugin"
+            else (flags.height, flags.width))
     sched_name = getattr(flags, "training_schedule", "long_schedule").lower()
     if sched_name not in SCHEDULES:
         raise ValueError("--training_schedule must be one of: %s" % ", ".join(sorted(SCHEDULES)))
@@ -99,7 +101,7 @@ def main(flags):
     step0 = tr.step_count
     end = step0 + flags.steps  # --steps counts the steps of THIS run; `step` is the global step (schedule, file names)
     for step, (a, b, f) in enumerate(load_batches(flags.list, flags.batch, pre, flags.augment, seed=flags.seed + rank,
-                                                  global_step=step0), step0 + 1):
+                                                  global_step=step0, augmentation=augmentation), step0 + 1):
         loss = tr.train_step(a, b, f)
         if step % flags.log_every == 0 or step == end:
             val = float(loss.item()) + (tr.l2_term() if flags.report_l2 else 0.0)
@@ -141,6 +143,10 @@ def parse_and_run(model):
     ap.add_argument("--batch", type=int, default=8, help="pairs per GPU (the reference's FlyingChairs batch size)")
     ap.add_argument("--dtype", default="f16x2", choices=["f32", "f16x2"])
     ap.add_argument("--no-augment", dest="augment", action="store_false")
+    ap.add_argument("--augmentation", default="plugin", choices=["plugin", "selflow"],
+                    help="plugin (default): the Caffe-style DataAugmentation / FlowAugmentation ops with their crop; selflow: "
+                         "what the reference's live loader applies to image pairs (augment_all_estimation: flips, channel "
+                         "permutation, colour chain per image; frames keep --height x --width)")
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--seed", type=int, default=1234)

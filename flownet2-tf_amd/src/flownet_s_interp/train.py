@@ -1,10 +1,13 @@
 """python -m src.flownet_s_interp.train --records fc_train_all.tfrecords --out ./logs [--steps N --batch 8
-                                        --add_hard_flow_mining hard|edges --lambda_weight 2 --hard_examples_perc 50]
+                                        --add_hard_flow_mining hard|edges --lambda_weight 2 --hard_examples_perc 50
+                                        --data_augmentation --invalid_like 1 --min_val_dense 1
+                                        --num_matches_distributions 3 --ff_like 1]
 The reference's src/flownet_s_interp/train.py + Net.train for the interpolation network over the HIP trainer: the
 FlowNetS tower on [image | 0.05 * sparse flow | match mask], heads without biases, the multiscale loss with optional
 hard-flow-example mining (flownet_s_interp.py:159-254), Adam on LONG_SCHEDULE, checkpoints (weights + Adam slots)
 under the reference's variable names.  Input: the reference's `image_matches` TFRecords (image_a, matches_a,
-sparse_flow, edges_a, flow); the interpolation-specific augmentation of the reference is not built."""
+sparse_flow, edges_a, flow).  --data_augmentation runs the reference loader's own augmentation (augment_all_interp) on
+the GPU (src/data_augmentation.py); it is off by default here and on by default in the reference."""
 import argparse
 import os
 import time
@@ -12,6 +15,17 @@ import time
 from ..dataloader import load_interp_batches
 from ..flownet_s.train import load_full_checkpoint, save_checkpoint, unpack_weights
 from ..training_schedules import LONG_SCHEDULE
+
+
+def str2bool(v):
+    """The reference's boolean flag type (train.py there): --flag, --flag true, --flag 0 ..."""
+    if isinstance(v, bool):
+        return v
+    if v.lower() in ("yes", "true", "t", "y", "1"):
+        return True
+    if v.lower() in ("no", "false", "f", "n", "0"):
+        return False
+    raise argparse.ArgumentTypeError("boolean value expected, got %r" % (v,))
 
 
 def main(flags):
@@ -35,7 +49,11 @@ def main(flags):
     os.makedirs(flags.out, exist_ok=True)
     step0, t0 = tr.step_count, time.perf_counter()
     end = step0 + flags.steps
-    batches = load_interp_batches(flags.records, flags.batch, (flags.height, flags.width), seed=flags.seed + rank)
+    batches = load_interp_batches(flags.records, flags.batch, (flags.height, flags.width), seed=flags.seed + rank,
+                                  data_augmentation=bool(getattr(flags, "data_augmentation", False)),
+                                  invalid_like=getattr(flags, "invalid_like", -1),
+                                  num_distrib=getattr(flags, "num_matches_distributions", 2),
+                                  min_val=getattr(flags, "min_val_dense", 0), ff_like=getattr(flags, "ff_like", -1))
     for step, (img, matches, sparse, edges, flow) in enumerate(batches, step0 + 1):
         loss = tr.forward_backward_interp(img, matches, sparse, flow, edges=edges, reduce=True)
         tr.apply_gradients(reduced_world=tr.wait_reduction())
@@ -64,6 +82,17 @@ if __name__ == "__main__":
     ap.add_argument("--add_hard_flow_mining", default="", choices=["", "hard", "edges"])
     ap.add_argument("--lambda_weight", type=float, default=2.0)
     ap.add_argument("--hard_examples_perc", type=float, default=50)
+    ap.add_argument("--data_augmentation", type=str2bool, nargs="?", const=True, default=False,
+                    help="augment every batch on the GPU as the reference's loader does (augment_all_interp: re-sampled "
+                         "matches, flips, channel permutation, colour chain).  Off by default here, because that is what "
+                         "this trainer has always done; the reference's flag defaults to true")
+    ap.add_argument("--invalid_like", type=int, default=-1,
+                    help="> 0: always sample the matches invalid-like (the ground truth with rectangular holes)")
+    ap.add_argument("--min_val_dense", type=int, default=0,
+                    help="0: sparse and dense density ranges; 1: dense ranges only")
+    ap.add_argument("--num_matches_distributions", type=int, default=2,
+                    help="1: the records' DeepMatching matches only; 2: those or uniformly sampled ones; 3: invalid-like too")
+    ap.add_argument("--ff_like", type=int, default=-1, help="> 0: dense densities from 65 %% to 85 %% only (FlowFields-like)")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--save-every", type=int, default=1000)

@@ -447,6 +447,75 @@ int fn2_augment_f32(const float* src, const float* transforms, const float* chro
 int fn2_flow_augmentation_f32(const float* flows, const float* transforms_from_a, const float* inv_transforms_from_b,
                               float* out, int n, int src_h, int src_w, int out_h, int out_w, void* stream);
 
+/* ---------------------------------------------------------------- SelFlow-style training augmentation
+ * What the reference's live loader applies to a training sample (src/dataloader.py:473-532): augment_all_interp
+ * (dataloader.py:35-80), augment_all_interp_validation (:83-90) and augment_all_estimation (:93-113) over the
+ * functions of src/data_augmentation.py:
+ *   fn2_selflow_stats  <- the two whole-sample quantities: sum(matches) of sample_from_distribution's almost-empty test
+ *                         (data_augmentation.py:513-521) and the channel means of tf.image.adjust_contrast inside
+ *                         distort_colour_zero..three (:30-63)
+ *   fn2_selflow_apply  <- sample_sparse_uniform :435-445, sample_sparse_invalid_like :449-479 (set_range_to_zero
+ *                         :263-275, mask_to_sparse_flow :324-338), sample_from_distribution :485-523,
+ *                         random_flip_with_flow :132-140 (flow_horizontal_flip / flow_vertical_flip :107-120),
+ *                         random_channel_swap(_single) :143-175, distort_colour :67-91
+ * perturbate_dm_matches (:341-366) and sample_sparse_grid_like (:372-432) are never called there and are not built.
+ *
+ * All tensors are dense fp32 NHWC on the device: images [n,h,w,3], matches / edges [n,h,w,1], flows [n,h,w,2] (8-byte
+ * aligned).  Outputs must not alias inputs (a flipped pixel is read from another place).  Every random decision is
+ * drawn on the host into one record per sample; the kernels are deterministic functions of inputs and records.
+ *
+ * Record: FN2_SELFLOW_PARAM_WORDS 32-bit words per sample, device array [n][FN2_SELFLOW_PARAM_WORDS]:
+ *   FN2_SF_DISTRIB       0 keep the DeepMatching mask and sparse flow, 1 uniform, 2 invalid-like
+ *   FN2_SF_THRESHOLD     uint32: distrib 1 sets the mask where u(i) < threshold;
+ *                        threshold = min(floor(p * 2^32), 2^32 - 1), p = density / 100 formed in float32
+ *   FN2_SF_KEY0, _KEY1   uint32 keys of the per-pixel hash
+ *   FN2_SF_N_RECT        0..3 rectangles in use; FN2_SF_RECTS + 4 r + (0..3) = (y0, x0, h, w) of rectangle r (int32):
+ *                        distrib 2 sets the mask everywhere except inside the rectangles
+ *   FN2_SF_FLIP_LR, FN2_SF_FLIP_UD   0 / 1
+ *   FN2_SF_PERM          0..5: out channel k = in channel row[k], rows (0,1,2) (0,2,1) (1,0,2) (1,2,0) (2,0,1) (2,1,0)
+ *   FN2_SF_COLOUR_ORDER  int32 0..3 = distort_colour_zero..three, -1 (anything else) = no colour distortion
+ *   FN2_SF_D_BRIGHTNESS, FN2_SF_F_SATURATION, FN2_SF_D_HUE, FN2_SF_F_CONTRAST   float32 bit patterns
+ *   remaining words: reserved, 0
+ * The hash (all arithmetic uint32, mod 2^32; i = y * w + x of the SOURCE pixel):
+ *   fmix32(x):  x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16
+ *   u(i) = fmix32(fmix32(i ^ key0) + key1)
+ * It stands in for tf.multinomial's i.i.d. Bernoulli per pixel; TensorFlow's random streams are not reproduced.
+ * Colour ops (TensorFlow's definitions): adjust_brightness x + d; adjust_contrast (x - mean_c) f + mean_c, mean_c over
+ * the sample's h x w; rgb_to_hsv v = max, range = v - min, s = v > 0 ? range / v : 0, h = (g - b) / (6 range) if r is the
+ * max, (b - r) / (6 range) + 2/6 if g is, else (r - g) / (6 range) + 4/6, 0 when range <= 0, + 1 when negative;
+ * hsv_to_rgb c = s v, m = v - c, dh = 6 h, x = c (1 - |dh mod 2 - 1|), the six cases of (int)dh (dh == 6 as case 0);
+ * adjust_saturation s <- clip(s f, 0, 1); adjust_hue h <- h + d wrapped into [0, 1).  Chains: zero B S H C, one S B C H,
+ * two C H B S, three H S C B; clip(., 0, 1) once after the chain, none between the ops. */
+#define FN2_SELFLOW_PARAM_WORDS 32
+enum {
+  FN2_SF_DISTRIB = 0, FN2_SF_THRESHOLD = 1, FN2_SF_KEY0 = 2, FN2_SF_KEY1 = 3, FN2_SF_N_RECT = 4, FN2_SF_RECTS = 5,
+  FN2_SF_FLIP_LR = 17, FN2_SF_FLIP_UD = 18, FN2_SF_PERM = 19, FN2_SF_COLOUR_ORDER = 20, FN2_SF_D_BRIGHTNESS = 21,
+  FN2_SF_F_SATURATION = 22, FN2_SF_D_HUE = 23, FN2_SF_F_CONTRAST = 24
+};
+/* Bytes of device workspace both entry points take for a batch (-1 for a bad size): per-sample mask counts and the
+ * [n][P][3] partial channel sums of each image, P a function of (h, w) only. */
+int64_t fn2_selflow_workspace_bytes(int n, int h, int w);
+/* Fills the workspace: (a) the number of pixels the re-sampled mask of each sample sets (distrib 1 / 2), integer block
+ * counts added with integer atomics; (b) per channel, the sum of each image as it stands in front of the contrast op of
+ * its sample's chain (after the permutation), one fp32 partial per block, reduced by wave shuffles and LDS, no float
+ * atomics; fn2_selflow_apply adds a sample's partials in index order.  image_a / image_b may be NULL (no sums);
+ * image_b takes the permutation of `params` and the colour fields of `params_b`. */
+int fn2_selflow_stats(const float* image_a, const float* image_b, const uint32_t* params, const uint32_t* params_b,
+                      void* workspace, int64_t ws_bytes, int n, int h, int w, void* stream);
+/* Every output pixel from its source pixel (the flipped position), in this order: re-sampled mask and sparse flow (the
+ * sparse flow is the ground truth where the mask is 1, else 0; when the mask would set less than 0.01 % of the pixels,
+ * 100 * count / (h w) < 0.01 in float32, or `flow` is NULL, matches and sparse_flow pass through), flips (flip_lr
+ * negates u, flip_ud negates v of both flows), channel permutation, colour chain, clip.  An output pointer that is NULL
+ * is not written and its input not read; a non-NULL output needs its input.  The image-pair form (augment_all_estimation)
+ * passes image_a, image_b and flow: both images share the flips and the permutation of `params`, image_b takes its colour
+ * fields from `params_b`.  The validation form is distrib 1 / 2 with colour_order -1 and no flips.  The workspace is the
+ * one fn2_selflow_stats filled for the same inputs and records on the same stream. */
+int fn2_selflow_apply(const float* image_a, const float* image_b, const float* matches, const float* sparse_flow,
+                      const float* edges, const float* flow, float* out_image_a, float* out_image_b, float* out_matches,
+                      float* out_sparse_flow, float* out_edges, float* out_flow, const uint32_t* params,
+                      const uint32_t* params_b, const void* workspace, int64_t ws_bytes, int n, int h, int w,
+                      void* stream);
+
 /* ---------------------------------------------------------------- variational refinement (EpicFlow)
  * The reference's src/SrcVariational binary, which utils.py:542-555 (calc_variational_inference_map) runs on the
  * network's cropped flow when Net.test / Net.test_batch get variational_refinement (net.py:578-589, :889-901):

@@ -5,6 +5,7 @@ bytes per sample), events on the launch stream, median of `--rounds` rounds of `
   python tools/bench_ops.py [--batch 8] [--height 384 --width 512] > profiles/rNN_ops_bandwidth.json
   python tools/bench_ops.py --interp [--batch 8 ...]    only the FlowNetS_interp input op against what it replaces
   python tools/bench_ops.py --occlusion --batch 4 --height 436 --width 1024    only the forward-backward occlusion check
+  python tools/bench_ops.py --selflow-augment           only the SelFlow-style training augmentation (8 x 384 x 512)
 """
 import argparse
 import json
@@ -121,6 +122,66 @@ def bench_occlusion(N, H, W, rounds, inner, rec):
     rec("tf_warp_f32_c2", ms, px * (8 + 8 + 8), "map + flow + output")
 
 
+def bench_selflow_augment(N, H, W, rounds, inner, rec):
+    """fn2_selflow_stats + fn2_selflow_apply on an `image_matches` batch with every stage on (uniform re-sampling, both
+    flips, a permutation, one chain order per sample), timed together as one augmentation and each by itself, then the NumPy
+    twin of the tests on the same batch (wall clock, one run) and a FlowNetS train step of the same batch size for scale.
+    Algorithmic bytes per pixel: stats reads the image (12 B); apply reads image, matches, sparse flow, edges and ground
+    truth (12 + 4 + 8 + 4 + 8 = 36 B) and writes the same five (36 B).  The buffers are reused launch after launch and fit the
+    256 MB last-level cache at the default size, so these are cache-warm times."""
+    import time
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import selflow_twin as twin
+    from src import data_augmentation as DA
+    dev = _hip.require_device()
+    lib, st, P_ = _hip.lib(), _hip.stream_ptr, _hip.ptr
+    rng = np.random.default_rng(3)
+    host = [rng.random((N, H, W, 3), dtype=np.float32), (rng.random((N, H, W, 1)) < 0.05).astype(np.float32),
+            rng.standard_normal((N, H, W, 2)).astype(np.float32), rng.random((N, H, W, 1), dtype=np.float32),
+            rng.standard_normal((N, H, W, 2)).astype(np.float32)]
+    table = DA.draw_interp_params(rng, N, H, W)
+    table[:, DA.DISTRIB] = DA.DISTRIB_UNIFORM
+    table[:, DA.THRESHOLD] = DA.density_threshold(25.0)
+    table[:, [DA.FLIP_LR, DA.FLIP_UD]] = 1
+    table.view(np.int32)[:, DA.COLOUR_ORDER] = np.arange(N) % 4
+    img, m, sf, ed, gt = (torch.from_numpy(x).to(dev) for x in host)
+    outs = [torch.empty_like(t) for t in (img, m, sf, ed, gt)]
+    par = torch.from_numpy(table.view(np.int32)).to(dev)
+    need = int(lib.fn2_selflow_workspace_bytes(N, H, W))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+    def stats():
+        _hip.check(lib.fn2_selflow_stats(P_(img), None, P_(par), None, P_(ws), need, N, H, W, st()))
+
+    def apply():
+        _hip.check(lib.fn2_selflow_apply(P_(img), None, P_(m), P_(sf), P_(ed), P_(gt), P_(outs[0]), None, P_(outs[1]),
+                                         P_(outs[2]), P_(outs[3]), P_(outs[4]), P_(par), None, P_(ws), need, N, H, W, st()))
+
+    def both():
+        stats(), apply()
+
+    px = N * H * W
+    rec("selflow_stats+apply", timed(both, rounds, inner), px * (12 + 36 + 36),
+        "both launches of one augmentation (+ the 4 N-byte memset of the counts); cache-warm")
+    rec("selflow_stats", timed(stats, rounds, inner), px * 12, "image once; cache-warm")
+    rec("selflow_apply", timed(apply, rounds, inner), px * 72, "five tensors in, five out; cache-warm")
+    t0 = time.perf_counter()
+    want = twin.apply(table, image_a=host[0], matches=host[1], sparse_flow=host[2], edges=host[3], flow=host[4])
+    t_twin = (time.perf_counter() - t0) * 1e3
+    err = float(np.abs(outs[0].cpu().numpy() - want["image_a"]).max())
+    rec("selflow_numpy_twin", t_twin, px * 72, "tests/selflow_twin.py (float64 colour) on the host, one run, wall clock; "
+        "max |GPU - twin| on the image %.2e" % err)
+    from src import weights as Wt
+    from src.trainer import FlowNetSTrainer
+    tr = FlowNetSTrainer(Wt.init_weights("FlowNetS", 1), N, H, W, dtype="f16x2", model="FlowNetS")
+    a, b, f = img, torch.flip(img, dims=(2,)).contiguous(), gt
+
+    def step():
+        tr.train_step(a, b, f)
+
+    rec("flownets_train_step_f16x2", timed(step, max(3, rounds // 3), 3), 0, "one FlowNetS train step of this batch, for scale")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -130,6 +191,8 @@ def main():
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--interp", action="store_true", help="only fn2_pack_interp_u8 and the sequence it replaces")
     ap.add_argument("--occlusion", action="store_true", help="only fn2_fb_occlusion and fn2_tf_warp_f32")
+    ap.add_argument("--selflow-augment", dest="selflow_augment", action="store_true",
+                    help="only fn2_selflow_stats + fn2_selflow_apply, their NumPy twin and a FlowNetS train step for scale")
     a = ap.parse_args()
     N, H, W = a.batch, a.height, a.width
     dev = _hip.require_device()
@@ -141,8 +204,8 @@ def main():
         out[name] = {"ms": round(ms, 5), "algorithmic_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / ms / 1e6, 1),
                      "frac_of_hbm_peak": round(nbytes / ms / 1e6 / HBM_PEAK, 4), "note": note}
 
-    if a.interp or a.occlusion:
-        (bench_interp if a.interp else bench_occlusion)(N, H, W, a.rounds, a.inner, rec)
+    if a.interp or a.occlusion or a.selflow_augment:
+        (bench_interp if a.interp else bench_occlusion if a.occlusion else bench_selflow_augment)(N, H, W, a.rounds, a.inner, rec)
         print(json.dumps({"batch": N, "height": H, "width": W, "hbm_peak_GBps": HBM_PEAK, "ops": out}, indent=1))
         return
     lib, st = _hip.lib(), _hip.stream_ptr
