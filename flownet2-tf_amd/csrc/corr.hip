@@ -283,64 +283,29 @@ extern "C" {
 int fn2_correlation_generic_f32(const float* a, const float* b, float* out, int n, int h, int w, int c,
                                 int k, int md, int s1, int s2, int pad, void* stream);
 
-int fn2_correlation_f32(const float* a, const float* b, float* out, int n, int h, int w, int c, int k, int md,
-                        int s1, int s2, int pad, void* stream) {
-  FN2_REQUIRE(a && b && out, "correlation: null pointer");
-  FN2_REQUIRE(n >= 1 && h >= 1 && w >= 1 && c >= 1, "input_a must have rank 4");  // correlation_kernel.cc:31
-  int oh, ow, gr, gw;
-  int rc = correlation_geometry(h, w, k, md, s1, s2, pad, &oh, &ow, &gr, &gw);
-  if (rc) return rc;
-  if (k == 1 && s1 == 1 && pad == md && corr2_ok(c, FN2_F32, md, s2, (long)n * h * w * c * 4))
-    return launch_corr2(a, c, 0, b, c, 0, out, gw * gw, 0, FN2_F32, FN2_F32, n, h, w, c, md, s2, gr, gw, FN2_ACT_NONE,
-                        (hipStream_t)stream);
-  if (!corr_fast_ok(c, 4, k, md, s1, s2, pad))
-    return fn2_correlation_generic_f32(a, b, out, n, h, w, c, k, md, s1, s2, pad, stream);
-  CorrArgs g;
-  g.a = a; g.b = b; g.out = out;
-  g.N = n; g.H = h; g.W = w;
-  g.a_cs = c; g.a_c0 = 0; g.b_cs = c; g.b_c0 = 0; g.out_cs = gw * gw; g.out_c0 = 0;
-  g.md = md; g.s2 = s2; g.gr = gr; g.gw = gw; g.lo = md - gr * s2;
-  g.act = FN2_ACT_NONE;
-  g.c_f = (float)c;
-  return launch_corr<float, float>(g, c, (hipStream_t)stream);
+// ---- kernel selection: ONE predicate chain per entry point, shared by the launch and by the host-only name query
+enum { CORR_SEL_GENERIC = 0, CORR_SEL_MFMA, CORR_SEL_CORR2, CORR_SEL_CORR3 };
+struct CorrSel {
+  int family;  // CORR_SEL_*
+  int lines;   // NL (corr2 / corr3: 128-byte channel lines) or NS (corr_mfma: 64-byte slabs); 0 for the generic kernel
+  int in_dtype, out_dtype;
+  int gr, gw;
+};
+
+static const char* corr_type_name(int dtype) {  // as rocprofv3 prints the template arguments
+  return dtype == FN2_F32 ? "float" : dtype == FN2_BF16 ? "__bf16" : dtype == FN2_F16 ? "_Float16" : "fn2::x2_t";
 }
 
-// The op surface on the split-fp16 matrix-core kernel (corr3.hip): fp32 features are rewritten once as split fp16
-// (x = hi + lo, 22 bits; the same 4 bytes per value) into a caller-provided workspace and multiplied with 3 fp16 MFMAs
-// per product instead of fp32 MFMAs at a sixteenth of the rate.  0 bytes = this geometry stays on fn2_correlation_f32.
-static bool corr_ws_path(int n, int h, int w, int c, int k, int md, int s1, int s2, int pad) {
-  return k == 1 && s1 == 1 && pad == md && c % 32 == 0 &&
-         corr3_ok(c, FN2_F16X2, FN2_F32, md, s2, h, 441, 0, (long)n * h * w * c * 4);
+static int corr_sel_name(const CorrSel& s, char* name, int cap) {
+  static const char* const kFamily[] = {"correlation_generic_kernel", "corr_mfma_kernel", "corr2_kernel", "corr3_kernel"};
+  if (s.family == CORR_SEL_GENERIC) snprintf(name, cap, "%s", kFamily[0]);
+  else snprintf(name, cap, "%s<%s, %s, %d>", kFamily[s.family], corr_type_name(s.in_dtype), corr_type_name(s.out_dtype), s.lines);
+  return FN2_OK;
 }
 
-int64_t fn2_correlation_workspace_bytes(int n, int h, int w, int c, int k, int md, int s1, int s2, int pad) {
-  if (n < 1 || h < 1 || w < 1 || c < 1) return 0;
-  return corr_ws_path(n, h, w, c, k, md, s1, s2, pad) ? 2 * (int64_t)n * h * w * c * 4 : 0;
-}
-
-int fn2_correlation_f32_ws(const float* a, const float* b, float* out, int n, int h, int w, int c, int k, int md,
-                           int s1, int s2, int pad, void* workspace, int64_t workspace_bytes, void* stream) {
-  FN2_REQUIRE(a && b && out, "correlation: null pointer");
-  FN2_REQUIRE(n >= 1 && h >= 1 && w >= 1 && c >= 1, "input_a must have rank 4");  // correlation_kernel.cc:31
-  const int64_t need = fn2_correlation_workspace_bytes(n, h, w, c, k, md, s1, s2, pad);
-  if (need == 0 || workspace == nullptr || workspace_bytes < need)
-    return fn2_correlation_f32(a, b, out, n, h, w, c, k, md, s1, s2, pad, stream);
-  int oh, ow, gr, gw;
-  int rc = correlation_geometry(h, w, k, md, s1, s2, pad, &oh, &ow, &gr, &gw);
-  if (rc) return rc;
-  const int64_t cnt = (int64_t)n * h * w * c;
-  char* wa = reinterpret_cast<char*>(workspace);
-  char* wb = wa + cnt * 4;
-  rc = fn2_to_f16x2(wa, a, nullptr, cnt, 1.f, stream);
-  if (rc) return rc;
-  rc = fn2_to_f16x2(wb, b, nullptr, cnt, 1.f, stream);
-  if (rc) return rc;
-  return launch_corr3(wa, c, 0, wb, c, 0, out, gw * gw, 0, FN2_F16X2, FN2_F32, n, h, w, c, md, s2, gr, gw, FN2_ACT_NONE,
-                      (hipStream_t)stream);
-}
-
-int fn2_correlation_fused(const fn2_tensor* a, const fn2_tensor* b, const fn2_tensor* out, int md, int s2,
-                          int act, void* stream) {
+// fn2_correlation_fused: argument checks, then corr3 -> corr2 -> corr_mfma -> FN2_ERR_UNSUPPORTED
+static int corr_fused_select(const fn2_tensor* a, const fn2_tensor* b, const fn2_tensor* out, int md, int s2,
+                             CorrSel* sel) {
   FN2_REQUIRE(a && b && out && a->data && b->data && out->data, "correlation_fused: null tensor");
   FN2_REQUIRE(a->dtype == b->dtype, "correlation_fused: a/b dtype mismatch");
   FN2_REQUIRE(a->n == b->n && a->h == b->h && a->w == b->w && a->c == b->c,
@@ -357,18 +322,135 @@ int fn2_correlation_fused(const fn2_tensor* a, const fn2_tensor* b, const fn2_te
                   (b->c0 * esz) % 16 == 0,
               "correlation_fused: feature views must be 16-byte aligned");
   FN2_REQUIRE(out->dtype == a->dtype || out->dtype == FN2_F32, "correlation_fused: bad output dtype");
-  if (corr3_ok(a->c, a->dtype, out->dtype, md, s2, a->h, out->cs, out->c0, (long)b->n * b->h * b->w * b->cs * esz))
-    return launch_corr3(a->data, a->cs, a->c0, b->data, b->cs, b->c0, out->data, out->cs, out->c0, a->dtype,
-                        out->dtype, a->n, a->h, a->w, a->c, md, s2, gr, gw, act, (hipStream_t)stream);
-  if (corr2_ok(a->c, a->dtype, md, s2, (long)b->n * b->h * b->w * b->cs * esz))
-    return launch_corr2(a->data, a->cs, a->c0, b->data, b->cs, b->c0, out->data, out->cs, out->c0, a->dtype,
-                        out->dtype, a->n, a->h, a->w, a->c, md, s2, gr, gw, act, (hipStream_t)stream);
+  sel->in_dtype = a->dtype; sel->out_dtype = out->dtype; sel->gr = gr; sel->gw = gw;
+  const long b_bytes = (long)b->n * b->h * b->w * b->cs * esz;
+  if (corr3_ok(a->c, a->dtype, out->dtype, md, s2, a->h, out->cs, out->c0, b_bytes)) {
+    sel->family = CORR_SEL_CORR3; sel->lines = a->c * esz / 128;
+    return FN2_OK;
+  }
+  if (corr2_ok(a->c, a->dtype, md, s2, b_bytes)) {
+    sel->family = CORR_SEL_CORR2; sel->lines = a->c * esz / 128;
+    return FN2_OK;
+  }
   if (!corr_fast_ok(a->c, esz, 1, md, 1, s2, md))
     return fail(FN2_ERR_UNSUPPORTED, "correlation_fused: C=%d md=%d s2=%d not covered by the MFMA kernel", a->c, md, s2);
-  FN2_REQUIRE(out->dtype == a->dtype || out->dtype == FN2_F32, "correlation_fused: bad output dtype");
   if (a->dtype == FN2_F16X2)
     FN2_REQUIRE(a->cs % 8 == 0 && a->c0 % 8 == 0 && b->cs % 8 == 0 && b->c0 % 8 == 0 && out->cs % 8 == 0,
                 "correlation_fused: split-fp16 views are group (8) aligned");
+  sel->family = CORR_SEL_MFMA; sel->lines = a->c * esz / 64;
+  return FN2_OK;
+}
+
+// The op surface on the split-fp16 matrix-core kernel (corr3.hip): fp32 features are rewritten once as split fp16
+// (x = hi + lo, 22 bits; the same 4 bytes per value) into a caller-provided workspace and multiplied with 3 fp16 MFMAs
+// per product instead of fp32 MFMAs at a sixteenth of the rate.  0 bytes = this geometry stays on fn2_correlation_f32.
+static bool corr_ws_path(int n, int h, int w, int c, int k, int md, int s1, int s2, int pad) {
+  return k == 1 && s1 == 1 && pad == md && c % 32 == 0 &&
+         corr3_ok(c, FN2_F16X2, FN2_F32, md, s2, h, 441, 0, (long)n * h * w * c * 4);
+}
+
+// fn2_correlation_f32 / fn2_correlation_f32_ws (use_ws: a sufficient workspace was given):
+// corr3 on split-fp16 copies -> corr2 -> corr_mfma -> the thread-per-element kernel
+static int corr_f32_select(int n, int h, int w, int c, int k, int md, int s1, int s2, int pad, bool use_ws,
+                           CorrSel* sel) {
+  FN2_REQUIRE(n >= 1 && h >= 1 && w >= 1 && c >= 1, "input_a must have rank 4");  // correlation_kernel.cc:31
+  int oh, ow;
+  int rc = correlation_geometry(h, w, k, md, s1, s2, pad, &oh, &ow, &sel->gr, &sel->gw);
+  if (rc) return rc;
+  sel->in_dtype = FN2_F32; sel->out_dtype = FN2_F32;
+  if (use_ws && corr_ws_path(n, h, w, c, k, md, s1, s2, pad)) {
+    sel->family = CORR_SEL_CORR3; sel->lines = c * 4 / 128; sel->in_dtype = FN2_F16X2;
+  } else if (k == 1 && s1 == 1 && pad == md && corr2_ok(c, FN2_F32, md, s2, (long)n * h * w * c * 4)) {
+    sel->family = CORR_SEL_CORR2; sel->lines = c * 4 / 128;
+  } else if (corr_fast_ok(c, 4, k, md, s1, s2, pad)) {
+    sel->family = CORR_SEL_MFMA; sel->lines = c * 4 / 64;
+  } else {
+    sel->family = CORR_SEL_GENERIC; sel->lines = 0;
+  }
+  return FN2_OK;
+}
+
+int64_t fn2_correlation_workspace_bytes(int n, int h, int w, int c, int k, int md, int s1, int s2, int pad) {
+  if (n < 1 || h < 1 || w < 1 || c < 1) return 0;
+  return corr_ws_path(n, h, w, c, k, md, s1, s2, pad) ? 2 * (int64_t)n * h * w * c * 4 : 0;
+}
+
+int fn2_correlation_f32_kernel_name(int n, int h, int w, int c, int k, int md, int s1, int s2, int pad,
+                                    int with_workspace, char* name, int cap) {
+  FN2_REQUIRE(name && cap > 0, "correlation_f32_kernel_name: no buffer");
+  name[0] = 0;
+  CorrSel sel;
+  int rc = corr_f32_select(n, h, w, c, k, md, s1, s2, pad, with_workspace != 0, &sel);
+  if (rc) return rc;
+  return corr_sel_name(sel, name, cap);
+}
+
+int fn2_correlation_f32(const float* a, const float* b, float* out, int n, int h, int w, int c, int k, int md,
+                        int s1, int s2, int pad, void* stream) {
+  FN2_REQUIRE(a && b && out, "correlation: null pointer");
+  CorrSel sel;
+  int rc = corr_f32_select(n, h, w, c, k, md, s1, s2, pad, false, &sel);
+  if (rc) return rc;
+  const int gr = sel.gr, gw = sel.gw;
+  if (sel.family == CORR_SEL_CORR2)
+    return launch_corr2(a, c, 0, b, c, 0, out, gw * gw, 0, FN2_F32, FN2_F32, n, h, w, c, md, s2, gr, gw, FN2_ACT_NONE,
+                        (hipStream_t)stream);
+  if (sel.family == CORR_SEL_GENERIC)
+    return fn2_correlation_generic_f32(a, b, out, n, h, w, c, k, md, s1, s2, pad, stream);
+  CorrArgs g;
+  g.a = a; g.b = b; g.out = out;
+  g.N = n; g.H = h; g.W = w;
+  g.a_cs = c; g.a_c0 = 0; g.b_cs = c; g.b_c0 = 0; g.out_cs = gw * gw; g.out_c0 = 0;
+  g.md = md; g.s2 = s2; g.gr = gr; g.gw = gw; g.lo = md - gr * s2;
+  g.act = FN2_ACT_NONE;
+  g.c_f = (float)c;
+  return launch_corr<float, float>(g, c, (hipStream_t)stream);
+}
+
+int fn2_correlation_f32_ws(const float* a, const float* b, float* out, int n, int h, int w, int c, int k, int md,
+                           int s1, int s2, int pad, void* workspace, int64_t workspace_bytes, void* stream) {
+  FN2_REQUIRE(a && b && out, "correlation: null pointer");
+  FN2_REQUIRE(n >= 1 && h >= 1 && w >= 1 && c >= 1, "input_a must have rank 4");  // correlation_kernel.cc:31
+  const int64_t need = fn2_correlation_workspace_bytes(n, h, w, c, k, md, s1, s2, pad);
+  if (need == 0 || workspace == nullptr || workspace_bytes < need)
+    return fn2_correlation_f32(a, b, out, n, h, w, c, k, md, s1, s2, pad, stream);
+  CorrSel sel;
+  int rc = corr_f32_select(n, h, w, c, k, md, s1, s2, pad, true, &sel);
+  if (rc) return rc;
+  const int gr = sel.gr, gw = sel.gw;
+  const int64_t cnt = (int64_t)n * h * w * c;
+  char* wa = reinterpret_cast<char*>(workspace);
+  char* wb = wa + cnt * 4;
+  rc = fn2_to_f16x2(wa, a, nullptr, cnt, 1.f, stream);
+  if (rc) return rc;
+  rc = fn2_to_f16x2(wb, b, nullptr, cnt, 1.f, stream);
+  if (rc) return rc;
+  return launch_corr3(wa, c, 0, wb, c, 0, out, gw * gw, 0, FN2_F16X2, FN2_F32, n, h, w, c, md, s2, gr, gw, FN2_ACT_NONE,
+                      (hipStream_t)stream);
+}
+
+int fn2_correlation_fused_kernel_name(const fn2_tensor* a, const fn2_tensor* b, const fn2_tensor* out, int md, int s2,
+                                      char* name, int cap) {
+  FN2_REQUIRE(name && cap > 0, "correlation_fused_kernel_name: no buffer");
+  name[0] = 0;
+  CorrSel sel;
+  int rc = corr_fused_select(a, b, out, md, s2, &sel);
+  if (rc) return rc;
+  return corr_sel_name(sel, name, cap);
+}
+
+int fn2_correlation_fused(const fn2_tensor* a, const fn2_tensor* b, const fn2_tensor* out, int md, int s2,
+                          int act, void* stream) {
+  CorrSel sel;
+  int rc = corr_fused_select(a, b, out, md, s2, &sel);
+  if (rc) return rc;
+  const int gr = sel.gr, gw = sel.gw;
+  if (sel.family == CORR_SEL_CORR3)
+    return launch_corr3(a->data, a->cs, a->c0, b->data, b->cs, b->c0, out->data, out->cs, out->c0, a->dtype,
+                        out->dtype, a->n, a->h, a->w, a->c, md, s2, gr, gw, act, (hipStream_t)stream);
+  if (sel.family == CORR_SEL_CORR2)
+    return launch_corr2(a->data, a->cs, a->c0, b->data, b->cs, b->c0, out->data, out->cs, out->c0, a->dtype,
+                        out->dtype, a->n, a->h, a->w, a->c, md, s2, gr, gw, act, (hipStream_t)stream);
   CorrArgs g;
   g.a = a->data; g.b = b->data; g.out = out->data;
   g.N = a->n; g.H = a->h; g.W = a->w;

@@ -6,9 +6,9 @@
 // per A row that uses it (21 times) -- 0.9 GB at batch 8; (2) a result run of 21 channels is written as 2-byte pieces
 // of 128-byte lines that other displacement rows complete much later; (3) a block walks 21 displacement rows x 4
 // stages one after the other with one stage in flight.  This kernel:
-//   * same-parity row quads: a block owns A rows y, y + 2, y + 4, y + 6 of a 32-pixel column block (8 waves = 4 rows
-//     x 2 column parities), which use the SAME displaced B rows but for three at each end -- 11 B rows serve 4 x 8
-//     (row, displacement-row) pairs instead of 32;
+//   * same-parity row pairs (C3_TY = 2, so H % 4 == 0): a block owns A rows y, y + 2 of a 64-pixel column block (8 waves
+//     = 2 rows x 2 column parities x 2 spans of 32 pixels), which use the SAME displaced B rows but for one at each end
+//     -- 9 B rows serve 2 x 8 (row, displacement-row) pairs instead of 16 (row quads were tried: DESIGN.md 7.23);
 //   * same-parity columns: a wave's 16 A pixels are x0 + 2i, the B window is de-interleaved by column parity at DMA
 //     time (the source address is per lane, so any permutation is free), and a 16 x 48 band holds the 21 even
 //     displacements of 16 pixels: 3 MFMA column tiles instead of 4 of 16 x 64 (21 of 48 computed columns are used);
@@ -283,7 +283,7 @@ static int launch3(const CorrArgs& a, int C, int b_bytes, hipStream_t s) {
 }
 
 // The FlowNetC attribute set on 16-bit / split-fp16 features, split-fp16
-// outputs group-aligned.  FN2_CORR3=0 keeps corr2 (A/B).  Rows in same-parity quads: H % 8 == 0.
+// outputs group-aligned.  FN2_CORR3=0 keeps corr2 (A/B).  Rows in same-parity pairs (C3_TY = 2): H % 4 == 0.
 bool corr3_ok(int C, int in_dtype, int out_dtype, int md, int s2, int H, int out_cs, int out_c0, long b_bytes) {
   const char* e = getenv("FN2_CORR3");
   if (e && atoi(e) == 0) return false;

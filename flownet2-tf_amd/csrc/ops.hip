@@ -639,15 +639,38 @@ int fn2_correlation_generic_f32(const float* a, const float* b, float* out, int 
   return FN2_OK;
 }
 
+// checks of fn2_correlation_grad_f32 and its choice: the tiled pair (FlowNetC attribute set) or the thread-per-element kernel
+static int corr_grad_select(int n, int h, int w, int c, int k, int md, int s1, int s2, int pad, int* oh, int* ow, int* gr,
+                            int* gw, bool* tiled) {
+  FN2_REQUIRE(n >= 1 && h >= 1 && w >= 1 && c >= 1, "correlation_grad: bad dims");
+  int rc = correlation_geometry(h, w, k, md, s1, s2, pad, oh, ow, gr, gw);
+  if (rc) return rc;
+  *tiled = k == 1 && s1 == 1 && s2 == 2 && md == 20 && pad == md && (long)n * ((c + 255) / 256) <= 65535 && h <= 65535;
+  return FN2_OK;
+}
+
+int fn2_correlation_grad_f32_kernel_name(int n, int h, int w, int c, int k, int md, int s1, int s2, int pad, char* name,
+                                         int cap) {
+  FN2_REQUIRE(name && cap > 0, "correlation_grad_f32_kernel_name: no buffer");
+  name[0] = 0;
+  int oh, ow, gr, gw;
+  bool tiled;
+  int rc = corr_grad_select(n, h, w, c, k, md, s1, s2, pad, &oh, &ow, &gr, &gw, &tiled);
+  if (rc) return rc;
+  // the tiled path is two launches (grad_a: true, grad_b: false); the name is the grad_a instantiation
+  snprintf(name, cap, "%s", tiled ? "correlation_grad_tiled_kernel<true, 16, 10, 2>" : "correlation_grad_kernel");
+  return FN2_OK;
+}
+
 int fn2_correlation_grad_f32(const float* g, const float* a, const float* b, float* da, float* db, int n,
                              int h, int w, int c, int k, int md, int s1, int s2, int pad, void* stream) {
   FN2_REQUIRE(g && a && b && da && db, "correlation_grad: null pointer");
-  FN2_REQUIRE(n >= 1 && h >= 1 && w >= 1 && c >= 1, "correlation_grad: bad dims");
   int oh, ow, gr, gw;
-  int rc = correlation_geometry(h, w, k, md, s1, s2, pad, &oh, &ow, &gr, &gw);
+  bool tiled;
+  int rc = corr_grad_select(n, h, w, c, k, md, s1, s2, pad, &oh, &ow, &gr, &gw, &tiled);
   if (rc) return rc;
   const long total = (long)n * h * w * c;
-  if (k == 1 && s1 == 1 && s2 == 2 && md == 20 && pad == md && (long)n * ((c + 255) / 256) <= 65535 && h <= 65535) {
+  if (tiled) {
     // the FlowNetC attribute set: tiled kernels, one launch per gradient
     const dim3 grid((w + 15) / 16, h, n * ((c + 255) / 256));
     hipLaunchKernelGGL((correlation_grad_tiled_kernel<true, 16, 10, 2>), grid, dim3(256), 0, (hipStream_t)stream, g, b, da,

@@ -59,7 +59,9 @@ PROTOTYPES = {
     "fn2_correlation_f32": (_i, [_p, _p, _p] + [_i] * 9 + [_p]),
     "fn2_correlation_workspace_bytes": (C.c_int64, [_i] * 9),
     "fn2_correlation_f32_ws": (_i, [_p, _p, _p] + [_i] * 9 + [_p, C.c_int64, _p]),
+    "fn2_correlation_f32_kernel_name": (_i, [_i] * 10 + [C.c_char_p, _i]),
     "fn2_correlation_grad_f32": (_i, [_p] * 5 + [_i] * 9 + [_p]),
+    "fn2_correlation_grad_f32_kernel_name": (_i, [_i] * 9 + [C.c_char_p, _i]),
     "fn2_flow_warp_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "fn2_flow_warp_grad_f32": (_i, [_p] * 5 + [_i] * 4 + [_p]),
     "fn2_downsample_f32": (_i, [_p, _p] + [_i] * 6 + [_p]),
@@ -90,6 +92,7 @@ PROTOTYPES = {
     "fn2_pack_image": (_i, [_p, _i, _tp, _i, _i, _p]),
     "fn2_pack_image_s2d": (_i, [_p, _i, _i, _i, _tp, _i, _i, _p]),
     "fn2_correlation_fused": (_i, [_tp, _tp, _tp, _i, _i, _i, _p]),
+    "fn2_correlation_fused_kernel_name": (_i, [_tp, _tp, _tp, _i, _i, C.c_char_p, _i]),
     "fn2_stack_input": (_i, [_p, _p, _p, _tp, _i, _p]),
     "fn2_fusion_input": (_i, [_p, _p, _p, _p, _tp, _i, _p]),
     "fn2_stack_input_pf": (_i, [_p, _p, _p, _i, _i, _f, _p, _tp, _i, _p]),

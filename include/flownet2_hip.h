@@ -98,19 +98,32 @@ int fn2_correlation_f32(const float* a, const float* b, float* out, int n, int h
                         void* stream);
 /* The same op with a caller-provided scratch buffer (the reference allocates its padded copies through
  * ctx->allocate_temp, correlation_kernel.cc:61-80): for the FlowNetC attribute set (kernel 1, max_displacement 20,
- * stride_2 2, pad 20; C % 32 == 0, H % 8 == 0) the features are rewritten as split fp16 (hi + lo, 22 bits) in the
- * workspace and the cost volume runs on the fp16 matrix cores (3 MFMAs per product); other geometries, a NULL or a too
- * small workspace fall through to fn2_correlation_f32.  fn2_correlation_workspace_bytes returns 0 for those. */
+ * stride_2 2, pad 20; C in {32, 64, 128, 256}, H % 4 == 0: corr3 works on same-parity row pairs) the features are
+ * rewritten as split fp16 (hi + lo, 22 bits) in the workspace and the cost volume runs on the fp16 matrix cores (3 MFMAs
+ * per product); other geometries, a NULL or a too small workspace fall through to fn2_correlation_f32.
+ * fn2_correlation_workspace_bytes returns 0 for those. */
 int64_t fn2_correlation_workspace_bytes(int n, int h, int w, int c, int kernel_size, int max_displacement, int stride_1,
                                         int stride_2, int pad);
 int fn2_correlation_f32_ws(const float* a, const float* b, float* out, int n, int h, int w, int c, int kernel_size,
                            int max_displacement, int stride_1, int stride_2, int pad, void* workspace,
                            int64_t workspace_bytes, void* stream);
+/* Host-only: the device kernel fn2_correlation_f32 (with_workspace == 0) or fn2_correlation_f32_ws with a sufficient
+ * workspace (with_workspace != 0) launches for these arguments, written as rocprofv3 prints the instantiation (without
+ * the "void fn2::" prefix and the argument list), e.g. "corr2_kernel<float, float, 1>"; "correlation_generic_kernel" for
+ * the thread-per-element fallback.  Same checks, same selection code and same return codes as the launch; launches
+ * nothing. */
+int fn2_correlation_f32_kernel_name(int n, int h, int w, int c, int kernel_size, int max_displacement, int stride_1,
+                                    int stride_2, int pad, int with_workspace, char* name, int cap);
 
 /* grad_a, grad_b (same shape as a) from grad_out (correlation_grad_kernel.cu.cc:20-189). */
 int fn2_correlation_grad_f32(const float* grad_out, const float* a, const float* b, float* grad_a,
                              float* grad_b, int n, int h, int w, int c, int kernel_size,
                              int max_displacement, int stride_1, int stride_2, int pad, void* stream);
+/* Host-only: "correlation_grad_tiled_kernel<true, 16, 10, 2>" when that call runs the tiled pair of kernels (grad_a:
+ * <true, ..>, grad_b: <false, ..>; kernel 1, stride_1 1, max_displacement 20, stride_2 2, pad 20), else
+ * "correlation_grad_kernel".  Same checks and selection code as the launch; launches nothing. */
+int fn2_correlation_grad_f32_kernel_name(int n, int h, int w, int c, int kernel_size, int max_displacement, int stride_1,
+                                         int stride_2, int pad, char* name, int cap);
 
 /* out[n,y,x,:] = bilinear(image[n], x+u, y+v) inside the image else 0 (flow_warp.cu.cc:44-95). */
 int fn2_flow_warp_f32(const float* image, const float* flow, float* out, int n, int h, int w, int c,
@@ -321,6 +334,16 @@ int fn2_pack_image_s2d(const float* img, int n_img, int h, int w, const fn2_tens
  * (flownet_c.py:40-46). */
 int fn2_correlation_fused(const fn2_tensor* a, const fn2_tensor* b, const fn2_tensor* out,
                           int max_displacement, int stride_2, int act, void* stream);
+/* Host-only: the kernel that call launches, e.g. "corr3_kernel<fn2::x2_t, fn2::x2_t, 8>" (the form of
+ * fn2_conv2d_kernel_name).  Runs the same argument checks and the same selection as fn2_correlation_fused (one function
+ * serves both) and returns the same codes; launches nothing and never dereferences the data pointers.  Selection:
+ *   corr3_kernel      16-bit / split-fp16 features, max_displacement 20, stride_2 2, H % 4 == 0, C * esz / 128 in
+ *                     {1, 2, 4, 8}; split-fp16 output only when its cs and c0 are multiples of 8; FN2_CORR3=0 disables it
+ *   corr2_kernel      any dtype, C * esz / 128 in {1, 2, 4, 8}, 64 + 2 * max_displacement <= 112 window pixels
+ *   corr_mfma_kernel  C * esz / 64 in {1, 2, 4, 8, 16} that corr2 did not take (in practice one 64-byte slab)
+ *   otherwise FN2_ERR_UNSUPPORTED (the generic kernel serves the fp32 op surface only). */
+int fn2_correlation_fused_kernel_name(const fn2_tensor* a, const fn2_tensor* b, const fn2_tensor* out,
+                                      int max_displacement, int stride_2, char* name, int cap);
 
 /* Stacked-net input (flownet_cs.py:21-36): out view (16-channel padded) =
  * [a(3) | b(3) | warp(b, flow)(3) | flow*0.05(2) | sqrt(sum_c (a-warp)^2)(1) | 0...]. */

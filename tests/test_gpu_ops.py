@@ -22,19 +22,32 @@ def surf():
 
 
 # ---- correlation ------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape,args", [
-    ((2, 12, 16, 32), (1, 20, 1, 2, 20)),     # call-site attrs (flownet_c.py:40) -> MFMA kernel, C=32
-    ((2, 16, 16, 32), (1, 20, 1, 2, 20)),     # the same on the row-quad kernel (corr3)
-    ((1, 6, 10, 256), (1, 20, 1, 2, 20)),     # call-site attrs, C=256, W < one tile
-    ((1, 9, 70, 64), (1, 20, 1, 2, 20)),      # W > 64: two x blocks, ragged second block
-    ((1, 8, 70, 64), (1, 20, 1, 2, 20)),      # H % 4 == 0 -> row-pair kernel (corr3), ragged second x block
-    ((2, 4, 7, 32), (1, 20, 1, 2, 20)),       # corr3, image smaller than the displacement range in both directions
-    ((1, 24, 130, 96), (1, 20, 1, 2, 20)),    # corr3, three x blocks, C = 96 (3 lines)
-    ((2, 7, 9, 16), (1, 4, 1, 1, 4)),         # s2 = 1 band, fp32 MFMA with 1 slab
-    ((1, 12, 14, 8), (3, 2, 2, 1, 3)),        # k=3, s1=2 -> generic kernel
-    ((1, 8, 8, 5), (1, 3, 1, 3, 3)),          # odd channel count -> generic kernel
-])
-def test_correlation_matches_oracle(surf, shape, args):
+X2F = "corr3_kernel<fn2::x2_t, float, %d>"   # the workspace entry: corr3 on split-fp16 copies of the fp32 features
+F32 = "%s_kernel<float, float, %d>"
+
+
+# the kernel each case takes is asserted through the host-only query (corr.hip's selection code), not assumed: corr3 needs
+# the call-site attributes, H % 4 == 0 and 1 / 2 / 4 / 8 channel lines of 128 bytes
+@pytest.mark.parametrize("shape,args,kernel", [
+    ((2, 12, 16, 32), (1, 20, 1, 2, 20), X2F % 1),              # call-site attrs (flownet_c.py:40), H % 4 == 0 -> corr3
+    ((2, 16, 16, 32), (1, 20, 1, 2, 20), X2F % 1),              # the same, two row-pair groups per parity more
+    ((1, 6, 10, 256), (1, 20, 1, 2, 20), F32 % ("corr2", 8)),   # H % 4 != 0 -> corr2 on fp32, C=256, W < one tile
+    ((1, 9, 70, 64), (1, 20, 1, 2, 20), F32 % ("corr2", 2)),    # W > 64: two x blocks, ragged second block
+    ((1, 8, 70, 64), (1, 20, 1, 2, 20), X2F % 2),               # H % 4 == 0 -> row-pair kernel (corr3), ragged second x block
+    ((2, 4, 7, 32), (1, 20, 1, 2, 20), X2F % 1),                # corr3, image smaller than the displacement range in both directions
+    ((1, 24, 130, 96), (1, 20, 1, 2, 20), "correlation_generic_kernel"),  # C = 96 is 3 lines: no matrix-core kernel, generic
+    ((2, 7, 9, 16), (1, 4, 1, 1, 4), F32 % ("corr_mfma", 1)),   # s2 = 1 band, one 64-byte slab -> fp32 MFMA kernel
+    ((1, 12, 14, 8), (3, 2, 2, 1, 3), "correlation_generic_kernel"),      # k=3, s1=2 -> generic kernel
+    ((1, 8, 8, 5), (1, 3, 1, 3, 3), "correlation_generic_kernel"),        # odd channel count -> generic kernel
+    ((1, 24, 130, 64), (1, 20, 1, 2, 20), X2F % 2),             # corr3, three x blocks, the last ragged
+], ids=["shape%d-args%d" % (i, i) for i in range(11)])
+def test_correlation_matches_oracle(surf, shape, args, kernel):
+    import ctypes
+    from src import _hip
+    lib, name = _hip.lib(), ctypes.create_string_buffer(128)
+    with_ws = lib.fn2_correlation_workspace_bytes(*shape, *args) > 0  # src.correlation passes a workspace when one is asked for
+    assert lib.fn2_correlation_f32_kernel_name(*shape, *args, int(with_ws), name, 128) == 0
+    assert name.value.decode() == kernel
     a, b = rnd(shape, 0), rnd(shape, 1)
     want = ref.correlation(a, b, *args)
     got = surf[0](a, b, *args)
