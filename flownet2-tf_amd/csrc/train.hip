@@ -301,6 +301,28 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ w, float*
 // that updates the fp32 master.  n[t] elements, l2[t] regulariser (0 for biases / transposed convs).
 struct AdamTensor { float* w; float* m; float* v; const float* g; x2_t* wx2; float scale; int frag_k; };  // frag_k: see x2_chunks
 static_assert(sizeof(AdamTensor) == 48, "the host builds the table as six 64-bit words per tensor");
+// The split-fp16 copy of updated master elements 4 i .. 4 i + 3 (w) / of element i (the scalar tail), as w * scale: one
+// store shared by every optimiser kernel, so the copy a kernel leaves is what fn2_to_f16x2 / fn2_to_f16x2_frag derive.
+__device__ __forceinline__ void store_weight_copy4(const AdamTensor& t, long i, const float4& w) {
+  if (t.wx2 == nullptr) return;
+  const float o[4] = {w.x * t.scale, w.y * t.scale, w.z * t.scale, w.w * t.scale};
+  if (t.frag_k == 0) {
+    store_vec<x2_t, 4>(t.wx2 + 4 * i, o);
+  } else {  // elements 4 i .. 4 i + 3 = half of group i / 2: 8 bytes of its hi chunk, 8 bytes of its lo chunk
+    typedef __attribute__((ext_vector_type(4))) _Float16 h4;
+    h4 h, l;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { h[j] = (_Float16)o[j]; l[j] = (_Float16)(o[j] - (float)h[j]); }
+    long ch, cl;
+    x2_chunks(i >> 1, t.frag_k, ch, cl);
+    char* base = reinterpret_cast<char*>(t.wx2);
+    *reinterpret_cast<h4*>(base + ch * 16 + (i & 1) * 8) = h;
+    *reinterpret_cast<h4*>(base + cl * 16 + (i & 1) * 8) = l;
+  }
+}
+__device__ __forceinline__ void store_weight_copy1(const AdamTensor& t, long i, float wi) {
+  if (t.wx2 != nullptr) store_elem<x2_t>(t.wx2 + i, wi * t.scale);
+}
 __device__ __forceinline__ void adam_tensor(const AdamTensor& t, long cnt, float reg, float lr_t, float b1, float b2,
                                             float eps, float gscale) {
   auto one = [&](float wi, float gi, float& mi, float& vi) {
@@ -318,28 +340,13 @@ __device__ __forceinline__ void adam_tensor(const AdamTensor& t, long cnt, float
     reinterpret_cast<float4*>(t.m)[i] = m;
     reinterpret_cast<float4*>(t.v)[i] = v;
     reinterpret_cast<float4*>(t.w)[i] = w;
-    if (t.wx2 != nullptr) {
-      const float o[4] = {w.x * t.scale, w.y * t.scale, w.z * t.scale, w.w * t.scale};
-      if (t.frag_k == 0) {
-        store_vec<x2_t, 4>(t.wx2 + 4 * i, o);
-      } else {  // elements 4 i .. 4 i + 3 = half of group i / 2: 8 bytes of its hi chunk, 8 bytes of its lo chunk
-        typedef __attribute__((ext_vector_type(4))) _Float16 h4;
-        h4 h, l;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { h[j] = (_Float16)o[j]; l[j] = (_Float16)(o[j] - (float)h[j]); }
-        long ch, cl;
-        x2_chunks(i >> 1, t.frag_k, ch, cl);
-        char* base = reinterpret_cast<char*>(t.wx2);
-        *reinterpret_cast<h4*>(base + ch * 16 + (i & 1) * 8) = h;
-        *reinterpret_cast<h4*>(base + cl * 16 + (i & 1) * 8) = l;
-      }
-    }
+    store_weight_copy4(t, i, w);
   }
   for (long i = 4 * n4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (long)gridDim.x * blockDim.x) {
     float mi = t.m[i], vi = t.v[i];
     const float wi = one(t.w[i], t.g[i], mi, vi);
     t.m[i] = mi; t.v[i] = vi; t.w[i] = wi;
-    if (t.wx2 != nullptr) store_elem<x2_t>(t.wx2 + i, wi * t.scale);
+    store_weight_copy1(t, i, wi);
   }
 }
 __global__ void __launch_bounds__(256) adam_multi_kernel(const AdamTensor* __restrict__ tab, const long* __restrict__ n,
@@ -353,6 +360,121 @@ __global__ void __launch_bounds__(256) adam_multi_kernel(const AdamTensor* __res
 __global__ void __launch_bounds__(256) adam_multi_dev_kernel(const AdamTensor* __restrict__ tab, const long* __restrict__ n,
                                                              const float* __restrict__ l2, const float* __restrict__ hyper) {
   adam_tensor(tab[blockIdx.y], n[blockIdx.y], l2[blockIdx.y], hyper[0], hyper[1], hyper[2], hyper[3], hyper[4]);
+}
+
+// The other optimisers of the reference's Net.train (net.py:1209-1288) and slim's per-tensor gradient clipping
+// (clip_gradient_norms = tf.clip_by_norm on each gradient, net.py:1381-1392), on the same table and grid as
+// adam_multi_dev_kernel.  hyper = {lr (lr_t for the Adam kinds), mu | beta1, beta2, eps, grad_scale, weight_decay,
+// clip_norm, 0}; G = grad_scale * g + reg * w is the gradient of the total loss, the quantity that is clipped.
+//
+// Pass 1 (only when clipping): block (x, t) writes the sum of G^2 over the elements it strides to partials[t * 128 + x]:
+// a fixed per-thread order, a fixed shuffle tree, four wave sums added in order -- no atomics, every slot written.
+__global__ void __launch_bounds__(256) optim_sumsq_kernel(const AdamTensor* __restrict__ tab, const long* __restrict__ n,
+                                                          const float* __restrict__ l2, const float* __restrict__ hyper,
+                                                          float* __restrict__ partials) {
+  const AdamTensor t = tab[blockIdx.y];
+  const long cnt = n[blockIdx.y];
+  const float reg = l2[blockIdx.y], gscale = hyper[4];
+  const long n4 = cnt >> 2;
+  float acc = 0.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const float4 g = reinterpret_cast<const float4*>(t.g)[i];
+    float4 G = {g.x * gscale, g.y * gscale, g.z * gscale, g.w * gscale};
+    if (reg != 0.f) {  // (block-uniform: an unregularised tensor's weights are not read)
+      const float4 w = reinterpret_cast<const float4*>(t.w)[i];
+      G.x = g.x * gscale + reg * w.x; G.y = g.y * gscale + reg * w.y;
+      G.z = g.z * gscale + reg * w.z; G.w = g.w * gscale + reg * w.w;
+    }
+    acc += G.x * G.x; acc += G.y * G.y; acc += G.z * G.z; acc += G.w * G.w;
+  }
+  for (long i = 4 * n4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (long)gridDim.x * blockDim.x) {
+    float G = t.g[i] * gscale;
+    if (reg != 0.f) G = t.g[i] * gscale + reg * t.w[i];
+    acc += G * G;
+  }
+  acc = wave_sum_t(acc);
+  __shared__ float s[4];
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[(long)blockIdx.y * gridDim.x + blockIdx.x] = ((s[0] + s[1]) + s[2]) + s[3];
+}
+
+// Pass 2: the update.  KIND (fn2_optim_kind) and CLIP are compile-time, so a kind's loop loads only the slots it has:
+// sgd none, momentum slot 0 (TF's ApplyMomentum with use_nesterov: a' = mu a + G, w' = w - (lr G + lr mu a')), the Adam
+// kinds both (adamw: Adam's update applied to w - weight_decay * w, G taken at the undecayed w).  CLIP: every block sums
+// its tensor's 128 partials in index order and scales G by clip_norm / max(sqrt(S), clip_norm) (S = 0: factor 1).
+template <int KIND, bool CLIP>
+__global__ void __launch_bounds__(256) optim_step_kernel(const AdamTensor* __restrict__ tab, const long* __restrict__ n,
+                                                         const float* __restrict__ l2, const float* __restrict__ hyper,
+                                                         const float* __restrict__ partials) {
+  constexpr bool SLOT0 = KIND != FN2_OPTIM_SGD, SLOT1 = KIND == FN2_OPTIM_ADAM || KIND == FN2_OPTIM_ADAMW;
+  const AdamTensor t = tab[blockIdx.y];
+  const long cnt = n[blockIdx.y];
+  const float reg = l2[blockIdx.y];
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], gscale = hyper[4], wd = hyper[5];
+  float c = 1.f;
+  if constexpr (CLIP) {
+    __shared__ float factor;
+    if (threadIdx.x == 0) {
+      const float* p = partials + (long)blockIdx.y * gridDim.x;
+      float S = 0.f;
+      for (int j = 0; j < (int)gridDim.x; ++j) S += p[j];
+      const float clip = hyper[6];
+      factor = clip / fmaxf(sqrtf(S), clip);
+    }
+    __syncthreads();
+    c = factor;
+  }
+  auto one = [&](float wi, float gi, float& mi, float& vi) {
+    gi = gi * gscale + reg * wi;
+    if constexpr (CLIP) gi *= c;
+    if constexpr (KIND == FN2_OPTIM_SGD) {
+      return wi - lr * gi;
+    } else if constexpr (KIND == FN2_OPTIM_MOMENTUM) {
+      mi = b1 * mi + gi;
+      return wi - (lr * gi + lr * b1 * mi);
+    } else {
+      if constexpr (KIND == FN2_OPTIM_ADAMW) wi = wi - wd * wi;
+      mi = b1 * mi + (1.f - b1) * gi;
+      vi = b2 * vi + (1.f - b2) * gi * gi;
+      return wi - lr * mi / (sqrtf(vi) + eps);
+    }
+  };
+  const long n4 = cnt >> 2;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    float4 w = reinterpret_cast<float4*>(t.w)[i], m = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (SLOT0) m = reinterpret_cast<float4*>(t.m)[i];
+    if constexpr (SLOT1) v = reinterpret_cast<float4*>(t.v)[i];
+    const float4 g = reinterpret_cast<const float4*>(t.g)[i];
+    w.x = one(w.x, g.x, m.x, v.x); w.y = one(w.y, g.y, m.y, v.y);
+    w.z = one(w.z, g.z, m.z, v.z); w.w = one(w.w, g.w, m.w, v.w);
+    if constexpr (SLOT0) reinterpret_cast<float4*>(t.m)[i] = m;
+    if constexpr (SLOT1) reinterpret_cast<float4*>(t.v)[i] = v;
+    reinterpret_cast<float4*>(t.w)[i] = w;
+    store_weight_copy4(t, i, w);
+  }
+  for (long i = 4 * n4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (long)gridDim.x * blockDim.x) {
+    float mi = 0.f, vi = 0.f;
+    if constexpr (SLOT0) mi = t.m[i];
+    if constexpr (SLOT1) vi = t.v[i];
+    const float wi = one(t.w[i], t.g[i], mi, vi);
+    if constexpr (SLOT0) t.m[i] = mi;
+    if constexpr (SLOT1) t.v[i] = vi;
+    t.w[i] = wi;
+    store_weight_copy1(t, i, wi);
+  }
+}
+
+template <int KIND>
+static void launch_optim_step(const void* table, const int64_t* counts, const float* l2, int n_tensors, const float* hyper,
+                              const float* partials, void* stream) {
+  const dim3 grid(FN2_OPTIM_PARTIALS, n_tensors), block(256);
+  if (partials != nullptr)
+    hipLaunchKernelGGL((optim_step_kernel<KIND, true>), grid, block, 0, (hipStream_t)stream, (const AdamTensor*)table,
+                       (const long*)counts, l2, hyper, partials);
+  else
+    hipLaunchKernelGGL((optim_step_kernel<KIND, false>), grid, block, 0, (hipStream_t)stream, (const AdamTensor*)table,
+                       (const long*)counts, l2, hyper, partials);
 }
 
 // upsample_flowXtoY backward (forward: conv-transpose 2->2, k4 s2 crop 1, upsample_flow_kernel in conv.hip):
@@ -1247,6 +1369,30 @@ int fn2_adam_step_multi_dev(const void* table, const int64_t* counts, const floa
   hipLaunchKernelGGL(adam_multi_dev_kernel, dim3(128, n_tensors), dim3(256), 0, (hipStream_t)stream,
                      (const AdamTensor*)table, (const long*)counts, l2, hyper);
   FN2_CHECK_LAUNCH("adam_multi_dev");
+  return FN2_OK;
+}
+
+int fn2_optim_grad_sumsq_multi(const void* table, const int64_t* counts, const float* l2, int n_tensors, const float* hyper,
+                               float* partials, void* stream) {
+  FN2_REQUIRE(table && counts && l2 && hyper && partials && n_tensors >= 1 && n_tensors <= 65535,
+              "optim_grad_sumsq_multi: bad arguments");
+  hipLaunchKernelGGL(optim_sumsq_kernel, dim3(FN2_OPTIM_PARTIALS, n_tensors), dim3(256), 0, (hipStream_t)stream,
+                     (const AdamTensor*)table, (const long*)counts, l2, hyper, partials);
+  FN2_CHECK_LAUNCH("optim_grad_sumsq_multi");
+  return FN2_OK;
+}
+
+int fn2_optim_step_multi_dev(int kind, const void* table, const int64_t* counts, const float* l2, int n_tensors,
+                             const float* hyper, const float* partials, void* stream) {
+  FN2_REQUIRE(table && counts && l2 && hyper && n_tensors >= 1 && n_tensors <= 65535, "optim_step_multi_dev: bad arguments");
+  FN2_REQUIRE(kind >= FN2_OPTIM_SGD && kind <= FN2_OPTIM_ADAMW, "optim_step_multi_dev: kind must be a fn2_optim_kind");
+  switch (kind) {
+    case FN2_OPTIM_SGD: launch_optim_step<FN2_OPTIM_SGD>(table, counts, l2, n_tensors, hyper, partials, stream); break;
+    case FN2_OPTIM_MOMENTUM: launch_optim_step<FN2_OPTIM_MOMENTUM>(table, counts, l2, n_tensors, hyper, partials, stream); break;
+    case FN2_OPTIM_ADAM: launch_optim_step<FN2_OPTIM_ADAM>(table, counts, l2, n_tensors, hyper, partials, stream); break;
+    default: launch_optim_step<FN2_OPTIM_ADAMW>(table, counts, l2, n_tensors, hyper, partials, stream); break;
+  }
+  FN2_CHECK_LAUNCH("optim_step_multi_dev");
   return FN2_OK;
 }
 

@@ -17,6 +17,8 @@ ACT_NONE, ACT_LEAKY = 0, 1
 OK = 0
 ERR_INVALID_ARGUMENT, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3
 MASK_F32, MASK_U8 = 0, 1
+OPTIM_KINDS = {"sgd": 0, "momentum": 1, "adam": 2, "adamw": 3}  # fn2_optim_kind
+OPTIM_PARTIALS = 128  # FN2_OPTIM_PARTIALS
 
 
 class Fn2Tensor(C.Structure):
@@ -107,7 +109,9 @@ PROTOTYPES = {
     "fn2_adam_step": (_i, [_p, _p, _p, _p, C.c_int64, _f, _f, _f, _f, _i, _f, _f, _p]),
     "fn2_adam_step_multi": (_i, [_p, _p, _p, _i, _f, _f, _f, _f, _i, _f, _p]),
     "fn2_adam_step_multi_dev": (_i, [_p, _p, _p, _i, _p, _p]),
-    "fn2_upsample_flow_bwd": (_i, [_tp, _p, _p, _p, _p, _i, _p]),
+    "fn2_optim_grad_sumsq_multi": (_i, [_p, _p, _p, _i, _p, _p, _p]),
+    "fn2_optim_step_multi_dev": (_i, [_i, _p, _p, _p, _i, _p, _p, _p]),
+    "fn2_upsample_flow_bwd":(_i, [_tp, _p, _p, _p, _p, _i, _p]),
     "fn2_head_bwd_filter": (_i, [_tp, _p, _p, _i, _i, _p]),
     "fn2_head_g18": (_i, [_p, _tp, _p]),
     "fn2_head_bwd_data": (_i, [_p, _p, _tp, _i, _i, _p]),

@@ -1,9 +1,10 @@
 """python -m src.flownet_s.train --list train.txt --out ./logs [--steps N --batch 8 --checkpoint w.npz --dtype f16x2
-                                 --ckpt-format npz|tf]
+                                 --ckpt-format npz|tf --training_schedule one_cycle --optimizer sgd|momentum|adamw
+                                 --momentum M | --min_momentum A --max_momentum B --weight_decay D --clip_grad_norm C]
 The reference's src/flownet_s/train.py:8-40 + Net.train (net.py:1002-1400) over the HIP trainer: FlyingChairs-style
-augmentation on the GPU, multiscale EPE loss, Adam on LONG_SCHEDULE, periodic .npz checkpoints under the reference's
-variable names.  Data: a list file of `image_a image_b flow.flo` triples (the reference's TFRecords are built from
-exactly these).  Under torch.distributed.run every rank trains on its own shuffling of the list (seed + rank) and
+augmentation on the GPU, multiscale EPE loss, Adam on LONG_SCHEDULE (or the optimiser and schedule named), periodic
+.npz checkpoints under the reference's variable names.  Data: a list file of `image_a image_b flow.flo` triples (the
+reference's TFRecords are built from exactly these).  Under torch.distributed.run every rank trains on its own shuffling of the list (seed + rank) and
 the gradients are all-reduced (data parallel)."""
 import argparse
 import os
@@ -67,6 +68,50 @@ def load_full_checkpoint(path):
     return W.load_weights(path)
 
 
+def add_optimizer_arguments(ap):
+    """--optimizer, --momentum, --min_momentum, --max_momentum, --weight_decay, --clip_grad_norm: names and defaults of
+    the reference's parser (flownet_s_interp/train.py:380-473); --optimizer unset means Adam."""
+    ap.add_argument("--optimizer", type=str.lower, default=None, choices=["adam", "sgd", "momentum", "adamw"],
+                    help="adam (default), sgd, momentum (SGD + Nesterov momentum) or adamw (Adam with decoupled weight decay)")
+    ap.add_argument("--momentum", type=float, default=None,
+                    help="constant momentum of --optimizer momentum; unset: cyclical between --min_momentum and "
+                         "--max_momentum along a computed schedule (clr, one_cycle, exp_decr, lr_range_test)")
+    ap.add_argument("--min_momentum", type=float, default=0.85, help="lower bound of the cyclical momentum")
+    ap.add_argument("--max_momentum", type=float, default=0.95, help="upper bound of the cyclical momentum")
+    ap.add_argument("--weight_decay", type=float, default=None,
+                    help="decoupled weight decay of adamw (default 1e-4); for momentum it replaces the schedule's L2 "
+                         "regularisation; sgd and adam ignore it")
+    ap.add_argument("--clip_grad_norm", type=float, default=-1.0,
+                    help="> 0: clip the norm of every gradient tensor to this value; <= 0 (default): off")
+
+
+def optimizer_kwargs(flags):
+    """The trainer's optimiser arguments from parsed flags (a namespace without them: the defaults, Adam)."""
+    return dict(optimizer=getattr(flags, "optimizer", None) or "adam", momentum=getattr(flags, "momentum", None),
+                min_momentum=getattr(flags, "min_momentum", 0.85), max_momentum=getattr(flags, "max_momentum", 0.95),
+                weight_decay=getattr(flags, "weight_decay", None), clip_grad_norm=getattr(flags, "clip_grad_norm", -1.0))
+
+
+POLICY_ARGUMENTS = (("clr_min_lr", float), ("clr_max_lr", float), ("clr_stepsize", int), ("clr_gamma", float),
+                    ("clr_mode", str), ("one_cycle_annealing_factor", float), ("start_lr", float), ("end_lr", float))
+
+
+def add_schedule_arguments(ap):
+    ap.add_argument("--training_schedule", default="long_schedule",
+                    help="long_schedule (default), fine_schedule, short_schedule, finetune_sintel_s1..5, finetune_kitti_s1..4, "
+                         "finetune_rob, clr, one_cycle, exp_decr, lr_range_test (src/training_schedules.py)")
+    for name, typ in POLICY_ARGUMENTS:
+        ap.add_argument("--" + name, type=typ, default=None)
+
+
+def schedule_of(flags):
+    """(schedule, parameters of the computed policies: clr / one_cycle / exp_decr / lr_range_test; net.py:1139-1190)."""
+    sched_name = getattr(flags, "training_schedule", "long_schedule").lower()
+    if sched_name not in SCHEDULES:
+        raise ValueError("--training_schedule must be one of: %s" % ", ".join(sorted(SCHEDULES)))
+    return SCHEDULES[sched_name], {k: getattr(flags, k) for k, _ in POLICY_ARGUMENTS if getattr(flags, k, None) is not None}
+
+
 def main(flags):
     import torch
     from .. import weights as W
@@ -83,14 +128,10 @@ def main(flags):
     augmentation = getattr(flags, "augmentation", "plugin")  # 'selflow' keeps the frame size: it has no crop
     h, w = ((pre["crop_height"], pre["crop_width"]) if flags.augment and augmentation == "plugin"
             else (flags.height, flags.width))
-    sched_name = getattr(flags, "training_schedule", "long_schedule").lower()
-    if sched_name not in SCHEDULES:
-        raise ValueError("--training_schedule must be one of: %s" % ", ".join(sorted(SCHEDULES)))
-    tr = FlowNetSTrainer(wts, flags.batch, h, w, schedule=SCHEDULES[sched_name], dtype=flags.dtype, model=model)
-    # parameters of the computed policies (clr / one_cycle / exp_decr / lr_range_test; net.py:1139-1190)
-    tr.train_params = {k: getattr(flags, k) for k in ("clr_min_lr", "clr_max_lr", "clr_stepsize", "clr_gamma", "clr_mode",
-                                                      "one_cycle_annealing_factor", "start_lr", "end_lr")
-                       if getattr(flags, k, None) is not None}
+    schedule, train_params = schedule_of(flags)
+    tr = FlowNetSTrainer(wts, flags.batch, h, w, schedule=schedule, dtype=flags.dtype, model=model,
+                         **optimizer_kwargs(flags))
+    tr.train_params = train_params
     if flags.checkpoint:  # Adam moments + global_step, when the checkpoint carries them (ours and the reference's do)
         state = load_full_checkpoint(flags.checkpoint)
         restored = tr.load_optimizer_state(state)
@@ -131,7 +172,7 @@ def main(flags):
     return tr
 
 
-def parse_and_run(model):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--list", required=True, help="text file of `image_a image_b flow.flo` triples, or a .tfrecords file of the "
                                                   "reference's converter (python -m src.tfrecord builds one)")
@@ -156,13 +197,13 @@ def parse_and_run(model):
     ap.add_argument("--val-list", dest="val_list", default=None, help="validation list file or .tfrecords (no augmentation)")
     ap.add_argument("--val-every", dest="val_every", type=int, default=0, help="validate every N steps (0 = never)")
     ap.add_argument("--val-batches", dest="val_batches", type=int, default=None, help="at most this many validation batches")
-    ap.add_argument("--training_schedule", default="long_schedule",
-                    help="long_schedule (default), fine_schedule, short_schedule, finetune_sintel_s1..5, finetune_kitti_s1..4, "
-                         "finetune_rob, clr, one_cycle, exp_decr, lr_range_test (src/training_schedules.py)")
-    for name, typ in (("clr_min_lr", float), ("clr_max_lr", float), ("clr_stepsize", int), ("clr_gamma", float),
-                      ("clr_mode", str), ("one_cycle_annealing_factor", float), ("start_lr", float), ("end_lr", float)):
-        ap.add_argument("--" + name, type=typ, default=None)
-    FLAGS = ap.parse_args()
+    add_schedule_arguments(ap)
+    add_optimizer_arguments(ap)
+    return ap
+
+
+def parse_and_run(model):
+    FLAGS = build_parser().parse_args()
     FLAGS.model = model
     if not os.path.exists(FLAGS.list):
         raise ValueError("list path must exist")

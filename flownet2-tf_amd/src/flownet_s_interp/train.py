@@ -1,10 +1,12 @@
 """python -m src.flownet_s_interp.train --records fc_train_all.tfrecords --out ./logs [--steps N --batch 8
                                         --add_hard_flow_mining hard|edges --lambda_weight 2 --hard_examples_perc 50
                                         --data_augmentation --invalid_like 1 --min_val_dense 1
-                                        --num_matches_distributions 3 --ff_like 1]
+                                        --num_matches_distributions 3 --ff_like 1
+                                        --training_schedule one_cycle --optimizer momentum --clip_grad_norm 1.0]
 The reference's src/flownet_s_interp/train.py + Net.train for the interpolation network over the HIP trainer: the
 FlowNetS tower on [image | 0.05 * sparse flow | match mask], heads without biases, the multiscale loss with optional
-hard-flow-example mining (flownet_s_interp.py:159-254), Adam on LONG_SCHEDULE, checkpoints (weights + Adam slots)
+hard-flow-example mining (flownet_s_interp.py:159-254), Adam on LONG_SCHEDULE unless --optimizer / --training_schedule
+(and the policy flags of src.flownet_s.train) say otherwise, checkpoints (weights + optimizer slots)
 under the reference's variable names.  Input: the reference's `image_matches` TFRecords (image_a, matches_a,
 sparse_flow, edges_a, flow).  --data_augmentation runs the reference loader's own augmentation (augment_all_interp) on
 the GPU (src/data_augmentation.py); it is off by default here and on by default in the reference."""
@@ -13,8 +15,8 @@ import os
 import time
 
 from ..dataloader import load_interp_batches
-from ..flownet_s.train import load_full_checkpoint, save_checkpoint, unpack_weights
-from ..training_schedules import LONG_SCHEDULE
+from ..flownet_s.train import (add_optimizer_arguments, add_schedule_arguments, load_full_checkpoint, optimizer_kwargs,
+                               save_checkpoint, schedule_of, unpack_weights)
 
 
 def str2bool(v):
@@ -41,9 +43,12 @@ def main(flags):
     wts = W.load_weights(flags.checkpoint) if flags.checkpoint else W.init_weights("FlowNetS_interp", flags.seed)
     for k in [k for k in wts if "/predict_flow" in k and k.endswith("/biases")]:
         del wts[k]  # no_deconv_biases (flownet_s_interp.py:78-95): a FlowNetS checkpoint's head biases are no variables here
-    tr = FlowNetSTrainer(wts, flags.batch, flags.height, flags.width, schedule=LONG_SCHEDULE, dtype=flags.dtype,
+    schedule, train_params = schedule_of(flags)  # (long_schedule unless --training_schedule says otherwise)
+    tr = FlowNetSTrainer(wts, flags.batch, flags.height, flags.width, schedule=schedule, dtype=flags.dtype,
                          model="FlowNetS_interp", add_hard_flow_mining=flags.add_hard_flow_mining,
-                         lambda_weight=flags.lambda_weight, hard_examples_perc=flags.hard_examples_perc)
+                         lambda_weight=flags.lambda_weight, hard_examples_perc=flags.hard_examples_perc,
+                         **optimizer_kwargs(flags))
+    tr.train_params = train_params
     if flags.checkpoint:
         tr.load_optimizer_state(load_full_checkpoint(flags.checkpoint))
     os.makedirs(flags.out, exist_ok=True)
@@ -68,7 +73,7 @@ def main(flags):
     return tr
 
 
-if __name__ == "__main__":
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", required=True, help=".tfrecords with image_a, matches_a, sparse_flow, edges_a, flow")
     ap.add_argument("--out", required=True)
@@ -96,7 +101,13 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--save-every", type=int, default=1000)
-    FLAGS = ap.parse_args()
+    add_schedule_arguments(ap)
+    add_optimizer_arguments(ap)
+    return ap
+
+
+if __name__ == "__main__":
+    FLAGS = build_parser().parse_args()
     if not os.path.exists(FLAGS.records):
         raise ValueError("records path must exist")
     main(FLAGS)

@@ -7,7 +7,8 @@ Reference semantics (what tf.gradients + tf.train.AdamOptimizer compute for it):
             average_endpoint_error (src/utils.py:209-224), compute_weighted_loss over the 5 scalars
             (weights .32 .08 .02 .01 .005, /5), + slim L2 regularisers (l2 = 4e-4 on slim.conv2d weights)
   optimiser Adam(lr from piecewise_constant LONG_SCHEDULE, beta 0.9/0.999, eps 1e-8), src/net.py:1205-1207,
-            :1290-1295; src/training_schedules.py:46-53
+            :1290-1295; src/training_schedules.py:46-53.  optimizer= 'sgd' | 'momentum' | 'adamw' and clip_grad_norm=
+            select the other optimisers of net.py:1209-1288 and slim's per-tensor clipping (fn2_optim_step_multi_dev)
   DP        not in the reference (single GPU).  Here: one process per GPU, each rank runs the step on its
             shard, ONE all-reduce of the flat gradient buffer, identical Adam on every rank.
 
@@ -62,10 +63,18 @@ def _index_hwio_uncached(rec):
 
 class FlowNetSTrainer:
     def __init__(self, weights, batch, height, width, schedule=LONG_SCHEDULE, eps=1e-8, dtype="f32", model="FlowNetS",
-                 add_hard_flow_mining="", lambda_weight=2.0, hard_examples_perc=50):
+                 add_hard_flow_mining="", lambda_weight=2.0, hard_examples_perc=50, optimizer="adam", momentum=None,
+                 min_momentum=0.85, max_momentum=0.95, weight_decay=None, clip_grad_norm=-1.0):
         """dtype 'f32': everything on the fp32 matrix cores.  'f16x2': activations, activation gradients and the
         weight copies the convolutions read are split fp16 (3 fp16 MFMAs per product, fp32 accumulate); the master
-        weights, their gradients and the Adam state stay fp32."""
+        weights, their gradients and the Adam state stay fp32.
+
+        optimizer (Net.train, net.py:1209-1288): 'adam' (default), 'sgd', 'momentum' (Nesterov; a fixed `momentum`, or
+        cyclical between min_momentum and max_momentum along a computed rate policy) or 'adamw' (decoupled
+        `weight_decay`, default 1e-4).  For 'momentum' a given weight_decay replaces the schedule's l2_regularization;
+        'sgd' and 'adam' ignore it.  clip_grad_norm > 0: every gradient tensor is clipped to that norm
+        (slim's clip_gradient_norms); <= 0: off."""
+        self._set_optimizer(optimizer, momentum, min_momentum, max_momentum, weight_decay, clip_grad_norm, schedule)
         if dtype not in ("f32", "f16x2"):
             raise ValueError("trainer dtype must be 'f32' or 'f16x2'")
         self.x2 = dtype == "f16x2"
@@ -128,6 +137,36 @@ class FlowNetSTrainer:
         self._build()
 
     # ------------------------------------------------------------------ construction
+    def _set_optimizer(self, optimizer, momentum, min_momentum, max_momentum, weight_decay, clip_grad_norm, schedule):
+        """Validate and record the optimiser arguments (host only: runs before the engine is built)."""
+        from .training_schedules import momentum_value
+        kind = "adam" if optimizer is None else str(optimizer).lower()
+        if kind not in _hip.OPTIM_KINDS:
+            raise ValueError("optimizer must be one of 'adam', 'sgd', 'momentum', 'adamw', not %r" % (optimizer,))
+        for name, val in (("momentum", momentum), ("min_momentum", min_momentum), ("max_momentum", max_momentum)):
+            if val is not None and not 0.0 <= float(val) < 1.0:
+                raise ValueError("%s must lie in [0, 1), not %r" % (name, val))
+        if weight_decay is not None and not float(weight_decay) >= 0.0:
+            raise ValueError("weight_decay must be >= 0, not %r" % (weight_decay,))
+        clip = float(clip_grad_norm)
+        if clip != clip or clip == float("inf"):
+            raise ValueError("clip_grad_norm must be finite (<= 0 disables clipping), not %r" % (clip_grad_norm,))
+        self.optimizer = kind
+        self.momentum = None if momentum is None else float(momentum)
+        self.min_momentum, self.max_momentum = min_momentum, max_momentum
+        self.clip_norm = clip if clip > 0.0 else 0.0
+        if kind == "momentum":
+            if momentum is None and (min_momentum is None or max_momentum is None):
+                raise ValueError("the momentum optimizer needs --momentum, or --min_momentum and --max_momentum")
+            momentum_value(schedule, 0, None, momentum, min_momentum, max_momentum)  # cyclical on a piecewise schedule raises
+        # decoupled decay of adamw (net.py:1267-1270); for momentum a given weight_decay IS the L2 coefficient (net.py:1221-1222)
+        self.weight_decay = (1e-4 if weight_decay is None else float(weight_decay)) if kind == "adamw" else 0.0
+        self.l2_reg = float(weight_decay) if kind == "momentum" and weight_decay is not None else schedule["l2_regularization"]
+        # slots per parameter: Adam's m and v, momentum's accumulator, none for sgd
+        self.n_slots = {"sgd": 0, "momentum": 1, "adam": 2, "adamw": 2}[kind]
+        # the default optimiser without clipping keeps its own entry points (fn2_adam_step_multi / _dev) and launches
+        self._optim_entry = not (kind == "adam" and self.clip_norm == 0.0)
+
     def _gbuf(self, buf):
         """Gradient buffer mirroring an activation buffer (fp32, same shape)."""
         key = buf.untyped_storage().data_ptr()
@@ -205,8 +244,8 @@ class FlowNetSTrainer:
                 params.append((rec["b"], False, None))
         total = sum(_round_up(t.numel(), 4) for t, _, _ in params)
         self.grad_arena = torch.zeros(total, dtype=torch.float32, device=self.dev)
-        self.m_arena = torch.zeros_like(self.grad_arena)
-        self.v_arena = torch.zeros_like(self.grad_arena)
+        self.m_arena = torch.zeros_like(self.grad_arena) if self.n_slots >= 1 else None   # Adam's m / the momentum accumulator
+        self.v_arena = torch.zeros_like(self.grad_arena) if self.n_slots >= 2 else None
         self.params = []
         off = 0
         last = None
@@ -216,7 +255,8 @@ class FlowNetSTrainer:
             # rec is None for a bias: it follows its layer's weight in `params`
             name = f"{rec['scope']}/{rec['name']}/weights" if rec is not None else f"{last['scope']}/{last['name']}/biases"
             last = rec if rec is not None else last
-            self.params.append(dict(w=t, g=g, m=self.m_arena[off:off + n], v=self.v_arena[off:off + n], reg=reg, n=n,
+            self.params.append(dict(w=t, g=g, m=self.m_arena[off:off + n] if self.n_slots >= 1 else None,
+                                    v=self.v_arena[off:off + n] if self.n_slots >= 2 else None, reg=reg, n=n,
                                     name=name, rec=rec))
             if rec is not None:
                 rec["dw"] = g
@@ -721,7 +761,7 @@ class FlowNetSTrainer:
 
     def l2_term(self):
         """0.5*l2*sum |W|^2 over the regularised weights (host-side report only)."""
-        l2 = self.schedule["l2_regularization"]
+        l2 = self.l2_reg
         return float(sum(0.5 * l2 * float((p["w"].double() ** 2).sum()) for p in self.params if p["reg"]))
 
     def apply_gradients(self, reduced_world=None):
@@ -730,9 +770,13 @@ class FlowNetSTrainer:
         # RCCL sum over xGMI; the mean is folded into Adam's grad_scale
         world = reduced_world if reduced_world is not None else allreduce_gradients(self.grad_arena)
         self.step_count += 1
+        if self._optim_entry:
+            self._upload_optim_hyper(world)
+            self._launch_optim(_hip.stream_ptr())
+            self.refresh_backward_weights(forward=False)
+            return
         lr = self.learning_rate(self.step_count - 1)
         b1, b2 = self.schedule["momentum"], self.schedule["momentum2"]
-        l2 = self.schedule["l2_regularization"]
         s = _hip.stream_ptr()
         if getattr(self, "_adam_table", None) is None:  # one launch for all parameter tensors
             self._build_adam_tables()
@@ -794,27 +838,87 @@ class FlowNetSTrainer:
         out[_index_hwio(rec).reshape(-1)] = arr.reshape(-1)
         return out
 
+    def _optim_hyper(self, world):
+        """The eight floats of fn2_optim_step_multi_dev for the step that self.step_count already counts: the rate and
+        the momentum are taken at the global step before the update, as the reference's graph reads them."""
+        step = self.step_count - 1
+        lr = self.learning_rate(step)
+        b1, b2 = self.schedule["momentum"], self.schedule["momentum2"]
+        if self.optimizer == "momentum":
+            from .training_schedules import momentum_value
+            b1 = momentum_value(self.schedule, step, getattr(self, "train_params", None), self.momentum,
+                                self.min_momentum, self.max_momentum)
+        elif self.optimizer in ("adam", "adamw"):
+            t = float(self.step_count)
+            lr = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+        return [lr, b1, b2, self.eps, 1.0 / (world * self.loss_scale), self.weight_decay, self.clip_norm, 0.0]
+
+    def _alloc_optim_buffers(self):
+        """The eight per-step floats (device + pinned staging) and, when clipping, the per-block partial sums; allocated
+        once, outside any capture."""
+        if getattr(self, "_ohyper", None) is not None:
+            return
+        self._ohyper = torch.zeros(8, dtype=torch.float32, device=self.dev)
+        self._ohyper_host = torch.zeros(8, dtype=torch.float32).pin_memory()
+        self._ohyper_done = None
+        if self.clip_norm > 0.0:  # (every slot is written by the first pass: no zeroing)
+            self._partials = torch.empty(len(self.params) * _hip.OPTIM_PARTIALS, dtype=torch.float32, device=self.dev)
+
+    def _upload_optim_hyper(self, world):
+        """Pinned staging as the captured Adam step's: the previous step's copy has been consumed once its update ran
+        (same stream order); the event makes the host wait for exactly that before overwriting the eight floats."""
+        self._alloc_optim_buffers()
+        if self._ohyper_done is not None:
+            self._ohyper_done.synchronize()
+        self._ohyper_host.copy_(torch.tensor(self._optim_hyper(world), dtype=torch.float32))
+        self._ohyper.copy_(self._ohyper_host, non_blocking=True)
+        self._ohyper_done = torch.cuda.Event()
+        self._ohyper_done.record()
+
+    def _launch_optim(self, s):
+        """The per-tensor squared norms (only when clipping) and the update: two launches for all parameter tensors."""
+        if getattr(self, "_adam_table", None) is None:
+            self._build_adam_tables()
+        args = (_hip.ptr(self._adam_table), _hip.ptr(self._adam_counts), _hip.ptr(self._adam_l2), len(self.params),
+                _hip.ptr(self._ohyper))
+        partials = None
+        if self.clip_norm > 0.0:
+            partials = _hip.ptr(self._partials)
+            _hip.check(self.lib.fn2_optim_grad_sumsq_multi(*args, partials, s))
+        _hip.check(self.lib.fn2_optim_step_multi_dev(_hip.OPTIM_KINDS[self.optimizer], *args, partials, s))
+
+    def _slots(self, p):
+        """[(TensorFlow slot suffix, tensor)] of parameter p under this optimiser."""
+        if self.optimizer == "momentum":
+            return [("/Momentum", p["m"])]
+        if self.optimizer == "sgd":
+            return []
+        return [("/Adam", p["m"]), ("/Adam_1", p["v"])]
+
     def optimizer_state(self):
         """Adam's moments and counters under TensorFlow's slot names, in the reference layouts: ``<var>/Adam`` (m),
         ``<var>/Adam_1`` (v), ``beta1_power``, ``beta2_power`` (tf.train.AdamOptimizer, net.py:1290-1295) and
         ``global_step`` -- what the reference's Saver writes next to the variables, so a resumed run continues the
-        moment estimates and the learning-rate schedule instead of restarting them."""
+        moment estimates and the learning-rate schedule instead of restarting them.  adamw writes the same names (the
+        generated class keeps the base optimiser's), momentum ``<var>/Momentum``, sgd nothing but ``global_step``."""
         b1, b2 = self.schedule["momentum"], self.schedule["momentum2"]
-        out = {"global_step": np.int64(self.step_count), "beta1_power": np.float32(b1 ** (self.step_count + 1)),
-               "beta2_power": np.float32(b2 ** (self.step_count + 1))}
+        out = {"global_step": np.int64(self.step_count)}
+        if self.n_slots == 2:
+            out.update(beta1_power=np.float32(b1 ** (self.step_count + 1)), beta2_power=np.float32(b2 ** (self.step_count + 1)))
         for p in self.params:
-            out[p["name"] + "/Adam"] = self._to_reference_layout(p, p["m"])
-            out[p["name"] + "/Adam_1"] = self._to_reference_layout(p, p["v"])
+            for suffix, slot in self._slots(p):
+                out[p["name"] + suffix] = self._to_reference_layout(p, slot)
         return out
 
     def load_optimizer_state(self, state):
         """Restore what optimizer_state() wrote (or a TensorFlow checkpoint of the reference holds).  Returns the
-        number of slot tensors restored; variables without slots keep zero moments."""
+        number of slot tensors restored; variables without slots keep zero moments.  Only this optimiser's own slots are
+        read: from a checkpoint written under another optimiser nothing but ``global_step`` is restored."""
         n = 0
         for p in self.params:
-            for suffix, dst in (("/Adam", p["m"]), ("/Adam_1", p["v"])):
+            for suffix, dst in self._slots(p):
                 if p["name"] + suffix in state:
-                    dst.copy_(torch.from_numpy(self._from_reference_layout(p, state[p["name"] + suffix])))
+                    dst.copy_(torch.from_numpy(np.array(self._from_reference_layout(p, state[p["name"] + suffix]))))
                     n += 1
         if "global_step" in state:
             self.step_count = int(np.asarray(state["global_step"]).reshape(-1)[0])
@@ -860,6 +964,10 @@ class FlowNetSTrainer:
                 for fn, args in ops:
                     _hip.check(fn(*args, s))
             return
+        if self._optim_entry:
+            self._launch_optim(s)
+            self.refresh_backward_weights(forward=False)
+            return
         if getattr(self, "_adam_table", None) is None:
             self._build_adam_tables()
         _hip.check(self.lib.fn2_adam_step_multi_dev(_hip.ptr(self._adam_table), _hip.ptr(self._adam_counts),
@@ -869,13 +977,14 @@ class FlowNetSTrainer:
     def _build_adam_tables(self):
         """{w, m, v, g, split-fp16 forward copy of w (or 0), its scale} per parameter tensor (fn2_adam_step_multi): Adam
         rewrites the copy the forward convolutions read while it has the new master in registers."""
-        l2 = self.schedule["l2_regularization"]
+        l2 = self.l2_reg
         fwd = {master.data_ptr(): (wx2.data_ptr(), scale, frag_k) for wx2, master, scale, frag_k in self.fwd_copies}
         ptrs = []
         for p in self.params:
             wx2, scale, frag_k = fwd.get(p["w"].data_ptr(), (0, 1.0, 0))
             bits = int(np.float32(scale).view(np.uint32)) | (int(frag_k) << 32)
-            ptrs.append([p["w"].data_ptr(), p["m"].data_ptr(), p["v"].data_ptr(), p["g"].data_ptr(), wx2, bits])
+            slot = lambda t: t.data_ptr() if t is not None else 0  # (a slot this optimiser lacks: null, never read)
+            ptrs.append([p["w"].data_ptr(), slot(p["m"]), slot(p["v"]), p["g"].data_ptr(), wx2, bits])
         self._adam_table = torch.tensor(ptrs, dtype=torch.int64, device=self.dev)
         self._adam_counts = torch.tensor([p["n"] for p in self.params], dtype=torch.int64, device=self.dev)
         self._adam_l2 = torch.tensor([l2 if p["reg"] else 0.0 for p in self.params], dtype=torch.float32, device=self.dev)
@@ -890,6 +999,8 @@ class FlowNetSTrainer:
         self._hyper = torch.zeros(5, dtype=torch.float32, device=self.dev)
         self._hyper_host = torch.zeros(5, dtype=torch.float32).pin_memory()
         self._build_adam_tables()
+        if self._optim_entry:
+            self._alloc_optim_buffers()
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream())
         graphs = []
@@ -917,18 +1028,21 @@ class FlowNetSTrainer:
         self.eng.set_inputs(input_a, input_b)
         world = world_size()
         self.step_count += 1
-        lr = self.learning_rate(self.step_count - 1)
-        b1, b2 = self.schedule["momentum"], self.schedule["momentum2"]
-        t = float(self.step_count)
-        lr_t = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
-        # pinned staging: the previous step's copy has been consumed once its Adam segment ran (same stream order);
-        # the event makes the host wait for exactly that before overwriting the five floats
-        if getattr(self, "_hyper_done", None) is not None:
-            self._hyper_done.synchronize()
-        self._hyper_host.copy_(torch.tensor([lr_t, b1, b2, self.eps, 1.0 / (world * self.loss_scale)], dtype=torch.float32))
-        self._hyper.copy_(self._hyper_host, non_blocking=True)
-        self._hyper_done = torch.cuda.Event()
-        self._hyper_done.record()
+        if self._optim_entry:
+            self._upload_optim_hyper(world)
+        else:
+            lr = self.learning_rate(self.step_count - 1)
+            b1, b2 = self.schedule["momentum"], self.schedule["momentum2"]
+            t = float(self.step_count)
+            lr_t = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+            # pinned staging: the previous step's copy has been consumed once its Adam segment ran (same stream order);
+            # the event makes the host wait for exactly that before overwriting the five floats
+            if getattr(self, "_hyper_done", None) is not None:
+                self._hyper_done.synchronize()
+            self._hyper_host.copy_(torch.tensor([lr_t, b1, b2, self.eps, 1.0 / (world * self.loss_scale)], dtype=torch.float32))
+            self._hyper.copy_(self._hyper_host, non_blocking=True)
+            self._hyper_done = torch.cuda.Event()
+            self._hyper_done.record()
         s = _hip.stream_ptr()
         pending = []
         for i in range(len(self._seg_ends)):

@@ -83,6 +83,47 @@ def cyclic_lr(step, base_lr, max_lr, step_size, gamma=0.99994, mode='triangular2
     return base_lr - clr if annealing else base_lr + clr
 
 
+def cyclic_momentum(step, base_mom, max_mom, step_size, gamma=0.99994, mode='triangular', one_cycle=False):
+    """utils.py:139-204 (cyclical momentum, arXiv 1803.09820: the mirror image of the cyclical rate):
+    cycle = floor(1 + step / (2 step_size)); x = |step / step_size - 2 cycle + 1|;
+    momentum = max - (max - base) * max(0, 1 - x), the amplitude halved per cycle ('triangular2') or scaled by
+    gamma**step ('exponential'); with one_cycle neither applies and the SECOND cycle (the annealing phase of the rate)
+    holds the momentum at max_mom."""
+    if mode not in ('triangular', 'triangular2', 'exponential'):
+        raise ValueError("mode must be 'triangular', 'triangular2' or 'exponential'")
+    import math
+    cycle = math.floor(1.0 + step / (2.0 * step_size))
+    if one_cycle and cycle == 2:
+        return max_mom
+    x = abs(step / step_size - 2.0 * cycle + 1.0)
+    cm = max(0.0, 1.0 - x) * (max_mom - base_mom)
+    if mode == 'triangular2' and not one_cycle:
+        cm /= float(2 ** int(cycle - 1))
+    if mode == 'exponential' and not one_cycle:
+        cm *= gamma ** step
+    return max_mom - cm
+
+
+def momentum_value(schedule, step, params=None, momentum=None, min_momentum=0.85, max_momentum=0.95):
+    """The momentum of the Momentum optimiser at global step `step`, selected as net.py:1224-1255: a fixed `momentum`
+    if given; otherwise cyclical between min_momentum and max_momentum with step_size = clr_stepsize (one_cycle set iff
+    the schedule is 'one_cycle'), or, under the LR range test, one decreasing half cycle over the test's iterations.
+    Cyclical momentum needs a computed rate policy: with a piecewise-constant schedule this raises ValueError (the
+    reference fails there on the schedule's list of rates)."""
+    if momentum is not None:
+        return momentum
+    lrs = schedule['learning_rates']
+    if not isinstance(lrs, str):
+        raise ValueError("cyclical momentum follows a computed learning-rate policy (clr, one_cycle, exp_decr, "
+                         "lr_range_test); with a piecewise-constant schedule give a fixed --momentum")
+    p = dict(DEFAULT_PARAMS, **(params or {}))
+    kind = lrs.lower()
+    if kind == 'range_test':
+        return cyclic_momentum(step, min_momentum, max_momentum, schedule['max_iters'], mode='triangular')
+    return cyclic_momentum(step, min_momentum, max_momentum, p['clr_stepsize'], mode='triangular',
+                           one_cycle=kind == 'one_cycle')
+
+
 def learning_rate(schedule, step, params=None):
     """The rate applied at global step `step` (0-based, as the reference's global_step tensor before the update)."""
     lrs = schedule['learning_rates']

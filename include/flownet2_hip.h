@@ -420,6 +420,31 @@ int fn2_adam_step_multi(const void* table, const int64_t* counts, const float* l
  * arguments are then the same every step, which lets the train step be captured once and replayed as a hipGraph. */
 int fn2_adam_step_multi_dev(const void* table, const int64_t* counts, const float* l2, int n_tensors, const float* hyper,
                             void* stream);
+/* The other optimisers Net.train selects from train_params_dict['optimizer'] (net.py:1209-1288) and the per-tensor
+ * gradient clipping it hands to slim.learning.create_train_op (clip_gradient_norm, net.py:1381-1392: tf.clip_by_norm on
+ * each gradient, not a global norm), on the table / counts / l2 arrays of fn2_adam_step_multi_dev.
+ *   G = grad_scale * g + l2 * w      the gradient of the total loss (the regulariser is part of it): what is clipped
+ *   clipping (clip_norm > 0)         S = sum G^2 over the tensor, G <- G * clip_norm / max(sqrt(S), clip_norm)
+ *   FN2_OPTIM_SGD       tf.train.GradientDescentOptimizer:  w' = w - lr G                      (no slots, words 1-2 unread)
+ *   FN2_OPTIM_MOMENTUM  tf.train.MomentumOptimizer(lr, mu, use_nesterov=True), TF's ApplyMomentum:
+ *                       a' = mu a + G,  w' = w - (lr G + lr mu a')                             (slot 0 = a, <var>/Momentum)
+ *   FN2_OPTIM_ADAM      fn2_adam_step_multi_dev's update on the (clipped) G
+ *   FN2_OPTIM_ADAMW     tf.contrib.opt.extend_with_decoupled_weight_decay(AdamOptimizer): w_d = w - weight_decay * w (not
+ *                       scaled by the rate, every tensor), G taken at the undecayed w, Adam's update applied to w_d
+ * hyper: eight floats in device memory {lr (lr_t for the Adam kinds), mu or beta1, beta2, eps, grad_scale, weight_decay,
+ * clip_norm, 0}, so both launches can be captured and replayed.  Every kind rewrites the split-fp16 copy of w as
+ * fn2_adam_step_multi does. */
+enum fn2_optim_kind { FN2_OPTIM_SGD = 0, FN2_OPTIM_MOMENTUM = 1, FN2_OPTIM_ADAM = 2, FN2_OPTIM_ADAMW = 3 };
+#define FN2_OPTIM_PARTIALS 128 /* floats of `partials` per tensor */
+/* Clipping, pass 1: partials[t * FN2_OPTIM_PARTIALS + x] = the sum of G^2 over the elements block x of tensor t strides
+ * (0 for a block without elements: the buffer needs no zeroing).  No atomics and a fixed summation order: the result is
+ * a function of the inputs' bits alone.  Writes nothing but `partials` (n_tensors * FN2_OPTIM_PARTIALS floats). */
+int fn2_optim_grad_sumsq_multi(const void* table, const int64_t* counts, const float* l2, int n_tensors, const float* hyper,
+                               float* partials, void* stream);
+/* The update of `kind`.  partials != NULL: clip with the sums of pass 1 (each block adds its tensor's partials in index
+ * order; hyper[6] = clip_norm > 0); NULL: no clipping, hyper[6] is not read. */
+int fn2_optim_step_multi_dev(int kind, const void* table, const int64_t* counts, const float* l2, int n_tensors,
+                             const float* hyper, const float* partials, void* stream);
 /* upsample_flowXtoY backward: g = gradient view [n,2h,2w,2] of its output slice, pf its fp32 input [n,h,w,2],
  * w [4][4][2][2] (ky, kx, o, i).  dpf = the input gradient, ADDED to dpf where accumulate != 0 and overwriting it where
  * accumulate == 0; dw += the filter gradient, always ADDED. */
