@@ -464,21 +464,18 @@ template <typename T, typename OutT>
 static int launch_conv(const ConvArgs& a, int tile, int phases_, hipStream_t s) {
   dim3 block(256);
   const int phases = phases_ * a.splitk;
-  if (tile == 128) {
-    dim3 grid(cdiv(a.M, 128), a.cout_pad / 128, phases);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, OutT, 4, 2, 2>), grid, block, 0, s, a);
-  } else if (tile == 64) {
-    dim3 grid(cdiv(a.M, 256), a.cout_pad / 64, phases);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, OutT, 4, 1, 4>), grid, block, 0, s, a);
-  } else if (tile == 32) {
-    dim3 grid(cdiv(a.M, 256), a.cout_pad / 32, phases);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, OutT, 2, 1, 4>), grid, block, 0, s, a);
-  } else {
-    dim3 grid(cdiv(a.M, 256), a.cout_pad / 16, phases);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, OutT, 1, 1, 4>), grid, block, 0, s, a);
-  }
-  FN2_CHECK_LAUNCH("conv_igemm");
-  return FN2_OK;
+#define FN2_LAUNCH1(BP, TILE, ...)                                                                                    \
+  do {                                                                                                                \
+    dim3 grid(cdiv(a.M, BP), a.cout_pad / TILE, phases);                                                              \
+    if (conv_name_sink().buf) FN2_CONV_NAME("conv_igemm_kernel<%s, %s, %s>", type_name<T>(), type_name<OutT>(), #__VA_ARGS__); \
+    else hipLaunchKernelGGL((conv_igemm_kernel<T, OutT, __VA_ARGS__>), grid, block, 0, s, a);                        \
+  } while (0)
+  if (tile == 128) FN2_LAUNCH1(128, 128, 4, 2, 2);
+  else if (tile == 64) FN2_LAUNCH1(256, 64, 4, 1, 4);
+  else if (tile == 32) FN2_LAUNCH1(256, 32, 2, 1, 4);
+  else FN2_LAUNCH1(256, 16, 1, 1, 4);
+#undef FN2_LAUNCH1
+  return conv_launched("conv_igemm");
 }
 
 // Second half of a flow head computed as a GEMM: fn2_conv2d first runs the head as a 1x1 convolution with
@@ -1253,8 +1250,7 @@ int fn2_conv2d_splits(const fn2_conv_desc* d) {
 int fn2_conv2d_kernel_name(const fn2_conv_desc* d, char* name, int cap) {
   FN2_REQUIRE(name && cap > 0, "conv2d_kernel_name: no buffer");
   name[0] = 0;
-  if (!d || d->wgt_layout < 1 || is_flow_head(d)) return FN2_OK;  // only the LDS-DMA launchers report their choice
-  conv_name_sink() = ConvNameSink{name, cap};
+  conv_name_sink() = ConvNameSink{name, cap};   // every launch site of fn2_conv2d writes its instantiation instead of launching
   const int rc = fn2_conv2d(d, nullptr);
   conv_name_sink() = ConvNameSink{nullptr, 0};
   return rc;
@@ -1274,16 +1270,17 @@ int fn2_conv2d(const fn2_conv_desc* d, void* stream) {
     } else {
       a.dbg &= ~16384;
     }
-    if (d->in.dtype == FN2_F32)
-      hipLaunchKernelGGL(flow_head_kernel<float>, dim3(blocks), dim3(256), 0, s, a);
-    else if (d->in.dtype == FN2_BF16)
-      hipLaunchKernelGGL(flow_head_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, a);
-    else if (d->in.dtype == FN2_F16)
-      hipLaunchKernelGGL(flow_head_kernel<f16_t>, dim3(blocks), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL(flow_head_kernel<x2_t>, dim3(blocks), dim3(256), 0, s, a);
-    FN2_CHECK_LAUNCH("flow_head");
-    return FN2_OK;
+#define FN2_HEAD(T)                                                                          \
+  do {                                                                                       \
+    if (conv_name_sink().buf) FN2_CONV_NAME("flow_head_kernel<%s>", type_name<T>());         \
+    else hipLaunchKernelGGL(flow_head_kernel<T>, dim3(blocks), dim3(256), 0, s, a);          \
+  } while (0)
+    if (d->in.dtype == FN2_F32) FN2_HEAD(float);
+    else if (d->in.dtype == FN2_BF16) FN2_HEAD(bf16_t);
+    else if (d->in.dtype == FN2_F16) FN2_HEAD(f16_t);
+    else FN2_HEAD(x2_t);
+#undef FN2_HEAD
+    return conv_launched("flow_head");
   }
   int sk = preferred_split(a, tile, phases);
   while (sk > 1 && (d->workspace == nullptr || split_bytes(a, sk) > d->workspace_bytes)) --sk;
@@ -1417,8 +1414,10 @@ int fn2_flow_head_tail_slabs(const float* t, int t_cs, int nslab, int64_t slab_s
   return FN2_OK;
 }
 
-int fn2_flow_head5(const fn2_tensor* x, const void* wgt, int cin_pad, int kpad, float out_scale, const float* bias, float* pf,
-                   int ring, const float* ring_w, const float* ring_b, void* stream) {
+// fn2_flow_head5 and fn2_flow_head5_kernel_name: the argument checks, the strip-or-tile decision and the launcher call
+// (which, with the name sink set, writes its instantiation and launches nothing)
+static int flow_head5(const fn2_tensor* x, const void* wgt, int cin_pad, int kpad, float out_scale, const float* bias, float* pf,
+                      int ring, const float* ring_w, const float* ring_b, void* stream) {
   int rc = check_view(x, "flow_head5 input");
   if (rc) return rc;
   FN2_REQUIRE(wgt && pf, "flow_head5: null pointer");
@@ -1471,6 +1470,21 @@ int fn2_flow_head5(const fn2_tensor* x, const void* wgt, int cin_pad, int kpad, 
     }
   }
   return launch_head5(a, (int)total, (hipStream_t)stream);
+}
+
+int fn2_flow_head5(const fn2_tensor* x, const void* wgt, int cin_pad, int kpad, float out_scale, const float* bias, float* pf,
+                   int ring, const float* ring_w, const float* ring_b, void* stream) {
+  return flow_head5(x, wgt, cin_pad, kpad, out_scale, bias, pf, ring, ring_w, ring_b, stream);
+}
+
+int fn2_flow_head5_kernel_name(const fn2_tensor* x, const void* wgt, int cin_pad, int kpad, float out_scale, const float* bias,
+                               float* pf, int ring, const float* ring_w, const float* ring_b, char* name, int cap) {
+  FN2_REQUIRE(name && cap > 0, "flow_head5_kernel_name: no buffer");
+  name[0] = 0;
+  conv_name_sink() = ConvNameSink{name, cap};
+  const int rc = flow_head5(x, wgt, cin_pad, kpad, out_scale, bias, pf, ring, ring_w, ring_b, nullptr);
+  conv_name_sink() = ConvNameSink{nullptr, 0};
+  return rc;
 }
 
 int fn2_flow_head_ring(const fn2_tensor* x, const float* wc, const float* bc, float* pf, void* stream) {

@@ -1711,12 +1711,6 @@ static bool launch_halo(const ConvArgs& a, int tile, int phases, hipStream_t s) 
   return true;
 }
 
-template <typename T> static const char* type_name();
-template <> const char* type_name<float>() { return "float"; }
-template <> const char* type_name<bf16_t>() { return "__bf16"; }
-template <> const char* type_name<f16_t>() { return "_Float16"; }
-template <> const char* type_name<x2_t>() { return "fn2::x2_t"; }
-
 ConvNameSink& conv_name_sink() {
   static thread_local ConvNameSink sink{nullptr, 0};
   return sink;
@@ -1809,23 +1803,24 @@ static int launch2(const ConvArgs& a, int tile, int phases, hipStream_t s) {
   else if (a.bp64) FN2_LAUNCH2(cdiv(a.M, 128), a.cout_pad / 32, 256, 1, 4, 1, 1, 2, 1);
   else FN2_LAUNCH2(cdiv(a.M, 256), a.cout_pad / 32, 256, 1, 4, 1, 2, 2, 1);
 #undef FN2_LAUNCH2
-  FN2_CHECK_LAUNCH("conv_igemm2");
-  return FN2_OK;
+  return conv_launched("conv_igemm2");
 }
 
 int launch_head5_strip(const ConvArgs& a, int blocks, hipStream_t s) {
-  if (a.ksteps == 3) hipLaunchKernelGGL((head5_strip_kernel<1>), dim3(blocks), dim3(512), 0, s, a);
-  else if (a.ksteps == 6) hipLaunchKernelGGL((head5_strip_kernel<2>), dim3(blocks), dim3(512), 0, s, a);
-  else return fail(FN2_ERR_UNSUPPORTED, "flow_head5 strip form: %d channel lines (3 or 6)", a.ksteps);
-  FN2_CHECK_LAUNCH("flow_head5_strip");
-  return FN2_OK;
+  if (a.ksteps != 3 && a.ksteps != 6) return fail(FN2_ERR_UNSUPPORTED, "flow_head5 strip form: %d channel lines (3 or 6)", a.ksteps);
+  if (conv_name_sink().buf) FN2_CONV_NAME("head5_strip_kernel<%d>", a.ksteps / 3);
+  else if (a.ksteps == 3) hipLaunchKernelGGL((head5_strip_kernel<1>), dim3(blocks), dim3(512), 0, s, a);
+  else hipLaunchKernelGGL((head5_strip_kernel<2>), dim3(blocks), dim3(512), 0, s, a);
+  return conv_launched("flow_head5_strip");
 }
 
 int launch_head5(const ConvArgs& a, int blocks, hipStream_t s) {
-  hipLaunchKernelGGL((conv_igemm2_kernel<x2_t, float, 1, 4, 2, 2, 2, 1, false, false, false, true>), dim3(blocks, 1, 1), dim3(256), 0,
-                     s, a);
-  FN2_CHECK_LAUNCH("flow_head5");
-  return FN2_OK;
+  if (conv_name_sink().buf)
+    FN2_CONV_NAME("conv_igemm2_kernel<fn2::x2_t, float, 1, 4, 2, 2, 2, 1, false, false, false, true>");
+  else
+    hipLaunchKernelGGL((conv_igemm2_kernel<x2_t, float, 1, 4, 2, 2, 2, 1, false, false, false, true>), dim3(blocks, 1, 1), dim3(256), 0,
+                       s, a);
+  return conv_launched("flow_head5");
 }
 
 bool conv_fast_ok(int in_dtype, int cin_pad, int cout) {
@@ -1845,13 +1840,13 @@ int launch_conv_fast(const ConvArgs& a, int in_dtype, int out_dtype, int tile, i
     return launch2<f16_t, float>(a, tile, phases, s);
   }
   if (out_dtype == FN2_F16X2) {
-    if (launch_rowrun<x2_t>(a, tile, phases, s)) { FN2_CHECK_LAUNCH("conv_rowrun"); return FN2_OK; }
-    if (launch_stem<x2_t>(a, tile, phases, s)) { FN2_CHECK_LAUNCH("conv_stem"); return FN2_OK; }
-    if (launch_halo<x2_t>(a, tile, phases, s)) { FN2_CHECK_LAUNCH("conv_halo"); return FN2_OK; }
+    if (launch_rowrun<x2_t>(a, tile, phases, s)) return conv_launched("conv_rowrun");
+    if (launch_stem<x2_t>(a, tile, phases, s)) return conv_launched("conv_stem");
+    if (launch_halo<x2_t>(a, tile, phases, s)) return conv_launched("conv_halo");
     if (a.merged) return fail(FN2_ERR_UNSUPPORTED, "conv2d kind 5: needs the halo kernel (input width a multiple of 128, no split-K)");
     return launch2<x2_t, x2_t>(a, tile, phases, s);
   }
-  if (launch_halo<float>(a, tile, phases, s)) { FN2_CHECK_LAUNCH("conv_halo"); return FN2_OK; }
+  if (launch_halo<float>(a, tile, phases, s)) return conv_launched("conv_halo");
   if (a.merged) return fail(FN2_ERR_UNSUPPORTED, "conv2d kind 5: needs the halo kernel (input width a multiple of 128, no split-K)");
   return launch2<x2_t, float>(a, tile, phases, s);
 }

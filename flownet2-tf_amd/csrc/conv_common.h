@@ -155,10 +155,26 @@ __device__ __forceinline__ void store4(OutT* p, float a, float b, float c, float
 // rocprofv3 prints it, without the "void fn2::" prefix and the argument list -- and launch nothing.
 struct ConvNameSink { char* buf; int cap; };
 ConvNameSink& conv_name_sink();
+#define FN2_CONV_NAME(...) snprintf(conv_name_sink().buf, conv_name_sink().cap, __VA_ARGS__)
+
+// What a launcher returns behind its hipLaunchKernelGGL: the runtime's verdict on the launch -- or, with the name sink
+// set, FN2_OK without a call into the HIP runtime (a name query is host-only and leaves the last-error slot alone).
+inline int conv_launched(const char* what) {
+  if (conv_name_sink().buf) return FN2_OK;
+  FN2_CHECK_LAUNCH(what);
+  return FN2_OK;
+}
+
+template <typename T> inline const char* type_name();
+template <> inline const char* type_name<float>() { return "float"; }
+template <> inline const char* type_name<bf16_t>() { return "__bf16"; }
+template <> inline const char* type_name<f16_t>() { return "_Float16"; }
+template <> inline const char* type_name<x2_t>() { return "fn2::x2_t"; }
 
 // conv2.hip: the fast path.  Returns FN2_ERR_UNSUPPORTED when (dtype, tile) has no instantiation.
 int launch_conv_fast(const ConvArgs& a, int in_dtype, int out_dtype, int tile, int phases, hipStream_t s);
 // conv2.hip: the composed 5x5 flow head (HEAD5 instantiation); `blocks` = n * tiles_y * tiles_x
+// (with the name sink set both write their instantiation and launch nothing)
 int launch_head5(const ConvArgs& a, int blocks, hipStream_t s);
 int launch_head5_strip(const ConvArgs& a, int blocks, hipStream_t s);
 // true when the fast kernel covers this geometry (then the packed weight must use the permuted-64 row order)

@@ -18,8 +18,8 @@ the fp32 MFMA parity path; "bf16" / "f16" the 16-bit MFMA throughput paths (acti
 weights 16-bit, fp32 accumulate, flow heads / warps / resize in fp32).
 """
 import ctypes as C
-import math
 import os
+import types
 
 import numpy as np
 import torch
@@ -30,35 +30,6 @@ from . import _hip, netdefs, weights as W
 # on the fp16 matrix cores; buffers are float32 containers (4 bytes per channel).
 _DT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "f16x2": torch.float32}
 _CODE = {"f32": _hip.FN2_F32, "bf16": _hip.FN2_BF16, "f16": _hip.FN2_F16, "f16x2": _hip.FN2_F16X2}
-_TILE_ARGS = {128: "2, 2, 2, 2", 64: "1, 4, 2, 2", 32: "1, 4, 1, 2"}  # conv_igemm2_kernel<.., WC, WP, TCN, TPN> per cout tile
-
-
-def conv2_kernel_args(tile, m, cout_pad, phases, x2=True):
-    """Template arguments <WC, WP, TCN, TPN, STAGES, KG, M16> of the conv_igemm2_kernel instantiation the library picks
-    (conv.hip: build_args / wants_bp64; conv2.hip: launch2), as rocprofv3 prints them."""
-    dbg = int(os.environ.get("FN2_CONV_DBG", "0"))
-    blocks64 = -(-m // 64) * (cout_pad // 128) * phases if tile == 128 else 0
-    # M16 (16x16x32 instruction): plain 128 x 64 tiles of large split-fp16 layers without split-K (conv2.hip: launch2)
-    big = "FN2_M16_MIN" in os.environ and blocks64 >= max(int(os.environ["FN2_M16_MIN"]), 513)  # off by default
-    m16 = "true" if (x2 and not dbg & 512 and (dbg & 1024 or big)) else "false"
-    full = dbg & 32
-    if tile < 128:
-        base = {64: "1, 4, 2, 2, 2, 1", 32: "1, 4, 1, 2, 2, 1"}[tile] if full else {64: "1, 4, 2, 1, 2, 1", 32: "1, 4, 1, 1, 2, 1"}[tile]
-        return f"{base}, {m16}"
-    blocks = -(-m // 64) * (cout_pad // 128) * phases
-    if not full and int(os.environ.get("FN2_KG", "1")):  # K groups (conv.hip: build_args): the 6x8 / 12x16 levels
-        if blocks <= int(os.environ.get("FN2_KG3_MAX", "0")):
-            return f"2, 2, 2, 1, 2, 3, {m16}"
-        if blocks <= int(os.environ.get("FN2_KG2_MAX", "95")):
-            return f"2, 2, 2, 1, 2, 2, {m16}"
-    if not full and blocks >= int(os.environ.get("FN2_BP64_MIN", "96")):
-        # 128 x 64 tiles; the 3-slot ring instantiation (STAGES = 3) for one-round grids without split-K (conv.hip)
-        ring = 384 <= blocks <= int(os.environ.get("FN2_RING_MAX", "512"))
-        return f"2, 2, 2, 1, 3, 1, {m16}" if ring else f"2, 2, 2, 1, 2, 1, {m16}"
-    return f"2, 2, 2, 2, 2, 1, {m16}"
-
-
-_TNAME = {"f32": "float", "bf16": "__bf16", "f16": "_Float16", "f16x2": "fn2::x2_t"}
 
 
 def _round_up(x, m):
@@ -192,7 +163,7 @@ class Engine:
         # compose_heads: FlowNetSD's / the fusion net's linear interconvN + predict_flowN pairs run as one composed 5x5
         # head (_composed_head).  Inference engines only (the trainer needs both variables); FN2_COMPOSE=0: off (A/B).
         self.compose_heads = bool(heads_as_gemm) and dtype == "f16x2" and bool(int(os.environ.get("FN2_COMPOSE", "1")))
-        self._head_t = None
+        self._head_t = {}           # (lane, floats per pixel) -> fp32 scratch of the GEMM-form heads (_gemm_head)
         self._defer_flow = False    # building a sub-network of a stack whose flow is resized by its consumer (_final_flow)
         self._own_ws = set()        # descriptors that keep a split-K workspace of their own (_head_slabs)
         self._pending_head = None   # a plain flow head waiting for the transposed conv that takes it along (_conv: defer_head)
@@ -302,6 +273,95 @@ class Engine:
         self.ops.append((name, fn, args))
         self.branch_of.append(self._branch)
 
+    # ------------------------------------------------------------------ packed convolution launches
+    def _cin_run(self, code, buf, c0, c, cout):
+        """(channels per tap, whole lines?) of a convolution that reads channels [c0, c0 + c) of `buf`: whole 128-byte
+        lines when the buffer has room (LDS-DMA kernel), else 8-aligned."""
+        line = _round_up(c, 128 // (2 if code in (_hip.FN2_BF16, _hip.FN2_F16) else 4))
+        if c0 + line <= buf.shape[3] and _hip.conv_plan(code, line, cout).layout == 1:
+            return line, True
+        return _round_up(c, 8), False
+
+    def _pack_weight(self, src, w_hwio, cout, pack, cin_pad=None, lds_only=False):
+        """Plan, pack, split-fp16 scaling and upload of the weight of a convolution reading the slice `src` = (buffer,
+        c0, c): fn2_conv2d_plan picks tile / layout / element type for (input dtype, channels per tap, cout);
+        `pack(w_hwio, cout_tile, kstep_elems, cin_pad, layout)` is one of weights.pack_*.  cin_pad: the channel run when the
+        caller fixes it (stems), else _cin_run's.  Returns the packing facts (w = device weight, cin_pad, cout_pad, kpad,
+        layout, tile, kstep, out_scale, wgt_dtype) -- or None, with lds_only, when the slice has no whole-line run."""
+        sbuf, sc0, sc = src
+        code = self._code(sbuf)
+        if cin_pad is None:
+            cin_pad, lines = self._cin_run(code, sbuf, sc0, sc, cout)
+            if lds_only and not lines:
+                return None
+        plan = _hip.conv_plan(code, cin_pad, cout)
+        assert plan.layout == 1 or not lds_only, (cin_pad, cout)
+        packed, cin_pad, cout_pad, kpad = pack(w_hwio, plan.cout_tile, plan.kstep_elems, cin_pad, plan.layout)
+        out_scale = 1.0
+        if plan.wgt_dtype == _hip.FN2_F16X2:
+            packed, out_scale = W.scale_f16x2(packed)   # the kernel multiplies the accumulator by out_scale = 2^-k (exact)
+        return types.SimpleNamespace(w=W.packed_to_device(packed, plan.wgt_dtype, self.device), cin_pad=cin_pad,
+                                     cout_pad=cout_pad, kpad=kpad, layout=plan.layout, tile=plan.cout_tile,
+                                     kstep=plan.kstep_elems, out_scale=out_scale, wgt_dtype=plan.wgt_dtype)
+
+    def _conv_desc(self, inp, out, pk, kind=0, k=1, stride=1, pad=0, act=False, bias=None, accumulate=False, lane=None):
+        """Fill an fn2_conv_desc (inp / out: fn2_tensor views; pk: the packing facts w, cin_pad, cout_pad, kpad, layout,
+        out_scale) and register it: kept alive with its bias (the weight stays with its owner), listed in conv_descs with
+        its lane -- _alloc_workspace sizes the lane's split-K scratch from that list.  The trainer's input-gradient
+        convolutions come through here as well."""
+        d = _hip.Fn2ConvDesc()
+        d.inp, d.out = inp, out
+        d.wgt = pk.w.data_ptr()
+        d.bias = bias.data_ptr() if bias is not None else None
+        d.kind = kind
+        d.kh = d.kw = k
+        d.stride, d.pad = stride, pad
+        d.act = _hip.ACT_LEAKY if act else _hip.ACT_NONE
+        d.cin_pad, d.cout_pad, d.kpad, d.wgt_layout = pk.cin_pad, pk.cout_pad, pk.kpad, pk.layout
+        d.accumulate = int(accumulate)
+        d.out_scale = pk.out_scale
+        self.keep += [d, bias]
+        self.conv_descs.append(d)
+        self.desc_branch.append(self._branch if lane is None else lane)
+        return d
+
+    def _packed_conv(self, src, dst, w_hwio, pack, kind=0, k=1, stride=1, pad=0, act=False, bias=None, cin_pad=None,
+                     fragments=False):
+        """One convolution launch from what its layer states: source and destination slices (buffer, c0, c), the weight
+        as the checkpoint holds it and the weights.pack_* that lays it out for `kind`, geometry, activation, bias.
+        Returns (descriptor, packing facts).  fragments: where the library would run the plain two-stage 128 x 64
+        instantiation, the split-fp16 weight goes to MFMA-fragment order (wgt_layout 2; pk.frag says so)."""
+        sbuf, sc0, sc = src
+        dbuf, dc0, dc = dst
+        pk = self._pack_weight(src, w_hwio, dc, pack, cin_pad)
+        d = self._conv_desc(self._v(sbuf, sc, sc0), self._v(dbuf, dc, dc0), pk, kind, k, stride, pad, act, bias)
+        # (layout = how the fp32 packed matrix is ordered -- what the trainer's index maps and filter gradients use;
+        # frag = the split-fp16 copy `w` the forward launch reads is that matrix re-tiled into fragment order)
+        pk.frag = bool(fragments and self.fragment_weights and pk.layout == 1 and pk.wgt_dtype == _hip.FN2_F16X2
+                       and pk.tile >= int(os.environ.get("FN2_WREG_TILE_MIN", "128")) and self._wants_fragments(d))
+        if pk.frag:
+            pk.w = W.to_fragment_order(pk.w)
+            d.wgt, d.wgt_layout = pk.w.data_ptr(), 2
+        self.keep.append(pk.w)
+        return d, pk
+
+    @staticmethod
+    def _layer_facts(pk):
+        """The packing keys of a layer record (what the trainer's index maps and filter gradients read)."""
+        return dict(w=pk.w, cin_pad=pk.cin_pad, cout_pad=pk.cout_pad, kpad=pk.kpad, layout=pk.layout, tile=pk.tile,
+                    kstep=pk.kstep)
+
+    def _upflow_rec(self, scope, name, src_f32, dst):
+        """Weight, bias, destination view and layer record of an upsample_flowXtoY, whichever launch carries it: its own
+        (_upflow), a head's tail (_head_tail) or a transposed conv (_conv: up_after).  Returns (w, b, view)."""
+        dbuf, dc0, dc = dst
+        w = W.to_device(self._w(f"{scope}/{name}/weights"), torch.float32, self.device)  # [4,4,2,2] HW-O-I
+        b = self._bias(scope, name, "deconv", 2)  # only the fusion net's two (flownet2.py:70-73, :86-89)
+        v = self._v(dbuf, dc, dc0)
+        self.keep += [w, b, v]
+        self.layers.append(dict(scope=scope, name=name, kind="upflow", src=src_f32, dst=dst, w=w, b=b, view=v))
+        return w, b, v
+
     # ------------------------------------------------------------------ layers
     def _conv(self, scope, spec, src, dst, up=None, up_after=None, defer_head=False):
         """src/dst: (buffer, c0, c).  One fn2_conv2d launch.  up (flow heads only): (name of the upsample_flowXtoY layer
@@ -322,98 +382,37 @@ class Engine:
                 and dbuf.dtype == torch.float32 and head_px >= int(os.environ.get("FN2_HEAD_GEMM_MIN", "8192"))
                 and self._head_gemm(scope, spec, src, dst, up)):
             return up is not None and bool(int(os.environ.get("FN2_FUSE_UPFLOW", "1")))
-        wname = f"{scope}/{name}/weights"
         in_code = self._code(sbuf)
         esz = 2 if in_code in (_hip.FN2_BF16, _hip.FN2_F16) else 4
-        # channels per tap: whole 128-byte lines when the buffer has room (LDS-DMA kernel), else 8-aligned
-        cin_pad = _round_up(cin, 8)
-        cin_line = _round_up(cin, 128 // esz)
-        if sc0 + cin_line <= sbuf.shape[3] and _hip.conv_plan(in_code, cin_line, cout).layout == 1:
-            cin_pad = cin_line
-        plan = _hip.conv_plan(in_code, cin_pad, cout)
-        tile, layout = plan.cout_tile, plan.layout
         # transposed convs with 16 outputs on wide maps (the fusion net's fuse_deconv0): both column phases of an output row
         # in one block (fn2_conv2d kind 5): 164.6 -> 116.9 us.  With 32 outputs (fuse_deconv1) the four-phase form has no
         # half-empty tile to begin with and the third tap slot only adds work: 39.8 -> 50.6 us, not taken.
-        # Inference engines only; FN2_DECONV_MERGED=0: off (A/B)
-        merged = (kind != "conv" and self.compose_heads and cout == 16 and in_code == _hip.FN2_F16X2 and layout == 1
-                  and tile == 32 and sbuf.shape[2] % 128 == 0 and bool(int(os.environ.get("FN2_DECONV_MERGED", "1"))))
-        if kind == "conv":
-            packed, cin_pad, cout_pad, kpad = W.pack_conv(self._w(wname), tile, plan.kstep_elems, cin_pad, layout)
-        elif merged:
-            packed, cin_pad, cout_pad, kpad = W.pack_deconv_merged(self._w(wname), tile, plan.kstep_elems, cin_pad, layout)
-        else:
-            packed, cin_pad, cout_pad, kpad = W.pack_deconv(self._w(wname), tile, plan.kstep_elems, cin_pad, layout)
+        # Inference engines only; FN2_DECONV_MERGED=0: off (A/B).  (16 outputs of a split-fp16 layer: the 32-row tile of the
+        # LDS-DMA kernel, the only plan fn2_conv2d_plan has for them)
+        merged = (kind != "conv" and self.compose_heads and cout == 16 and in_code == _hip.FN2_F16X2
+                  and sbuf.shape[2] % 128 == 0 and bool(int(os.environ.get("FN2_DECONV_MERGED", "1"))))
+        pack, dkind = (W.pack_conv, 0) if kind == "conv" else (W.pack_deconv_merged, 5) if merged else (W.pack_deconv, 1)
+        w_var = self._w(f"{scope}/{name}/weights")
         bias = self._bias(scope, name, kind, cout)  # transposed convs: only where the graph declares one (fusion net)
-        out_scale = 1.0
-        if plan.wgt_dtype == _hip.FN2_F16X2:
-            # split fp16: scale the weights by 2^k so that max|w| ~ 1024 (lo parts stay normal fp16 numbers
-            # over 4 decades of weight magnitude); the kernel multiplies the accumulator by 2^-k (exact)
-            wmax = float(abs(packed).max())
-            if wmax > 0:
-                k2 = int(math.floor(math.log2(1024.0 / wmax)))
-                packed = packed * (2.0 ** k2)
-                out_scale = 2.0 ** (-k2)
-        wdev = W.packed_to_device(packed, plan.wgt_dtype, self.device)
-        d = _hip.Fn2ConvDesc()
-        d.inp = self._v(sbuf, sc, sc0)
-        d.out = self._v(dbuf, dc, dc0)
-        d.wgt = wdev.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.kind = 0 if kind == "conv" else (5 if merged else 1)
-        d.kh = d.kw = k
-        d.stride, d.pad = stride, pad
-        d.act = _hip.ACT_LEAKY if act else _hip.ACT_NONE
-        d.cin_pad, d.cout_pad, d.kpad = cin_pad, cout_pad, kpad
-        d.wgt_layout = layout
-        d.out_scale = out_scale
-        frag = False
-        if (self.fragment_weights and layout == 1 and tile >= int(os.environ.get("FN2_WREG_TILE_MIN", "128"))
-                and plan.wgt_dtype == _hip.FN2_F16X2 and self._wants_fragments(d)):
-            wdev = W.to_fragment_order(wdev)
-            d.wgt, d.wgt_layout, frag = wdev.data_ptr(), 2, True
-        self.keep += [d, wdev, bias]
-        self.conv_descs.append(d)
-        self.desc_branch.append(self._branch)
-        up_rec = None
+        d, pk = self._packed_conv(src, dst, w_var, pack, dkind, k, stride, pad, act, bias, fragments=True)
         if self._pending_head is not None and kind != "conv":
             hd = self._pending_head
             assert up_after is not None and hd.inp.data == d.inp.data and hd.inp.c0 == d.inp.c0, (scope, name)
             d.head = C.addressof(hd)
             self._pending_head = None
+        self.layers.append(dict(scope=scope, name=name, kind=d.kind, k=k, stride=stride, pad=pad, cin=cin, cout=cout,
+                                act=bool(act), src=src, dst=dst, desc=d, b=bias, frag=pk.frag, **self._layer_facts(pk)))
         if up_after is not None:
             assert kind != "conv" and (not merged or cout == 16)   # (kind 5 with 16 outputs: its epilogue writes the two channels)
             up_name, up_src, (ubuf, uc0, uc) = up_after
             assert ubuf is dbuf and uc == 2
-            uw = W.to_device(self._w(f"{scope}/{up_name}/weights"), torch.float32, self.device)
-            ub = self._bias(scope, up_name, "deconv", 2)
+            uw, ub, _ = self._upflow_rec(scope, up_name, up_src, up_after[2])
             d.up_src, d.up_w, d.up_bias, d.up_c0 = up_src.data_ptr(), uw.data_ptr(), (ub.data_ptr() if ub is not None else None), uc0
-            uv = self._v(ubuf, uc, uc0)
-            self.keep += [uw, ub, uv]
-            up_rec = dict(scope=scope, name=up_name, kind="upflow", src=up_src, dst=up_after[2], w=uw, b=ub, view=uv)
-        # (layout = how the fp32 packed matrix is ordered -- what the trainer's index maps and filter gradients use;
-        # frag = the split-fp16 copy `w` the forward launch reads is that matrix re-tiled into fragment order)
-        self.layers.append(dict(scope=scope, name=name, kind=d.kind, k=k, stride=stride, pad=pad, cin=cin, cout=cout,
-                                act=bool(act), src=src, dst=dst, desc=d, w=wdev, b=bias, cin_pad=cin_pad,
-                                cout_pad=cout_pad, kpad=kpad, layout=layout, tile=tile, kstep=plan.kstep_elems, frag=frag))
-        if up_rec is not None:
-            self.layers.append(up_rec)
-        tn = _TNAME[self.dtype_name] if in_code == self.act_code else "float"
-        if kind == "conv" and cout == 2 and k == 3 and stride == 1 and pad == 1:
-            kern = f"flow_head_kernel<{tn}>"
-        elif layout == 1:
-            on = _TNAME[self.dtype_name] if self._code(dbuf) == self.act_code else "float"
-            m_px = dbuf.shape[0] * dbuf.shape[1] * dbuf.shape[2] // (4 if kind != "conv" else 1)
-            kern = f"conv_igemm2_kernel<{tn}, {on}, {conv2_kernel_args(tile, m_px, cout_pad, 4 if kind != 'conv' else 1, tn == 'fn2::x2_t')}>"
-        else:
-            shape = {128: "4, 2, 2", 64: "4, 1, 4", 32: "2, 1, 4", 16: "1, 1, 4"}[tile]
-            on = _TNAME[self.dtype_name] if self._code(dbuf) == self.act_code else "float"
-            kern = f"conv_igemm_kernel<{tn}, {on}, {shape}>"
-        if defer_head and kern.startswith("flow_head_kernel"):
+        if defer_head and kind == "conv" and cout == 2 and k == 3 and stride == 1 and pad == 1:   # (a plain flow head)
             assert self._pending_head is None
             self._pending_head = d
         else:
-            self._op(f"{scope}/{name}", self.lib.fn2_conv2d, C.byref(d), kernel=kern)
+            self._op(f"{scope}/{name}", self.lib.fn2_conv2d, C.byref(d))
         n, oh, ow = dbuf.shape[0], dbuf.shape[1], dbuf.shape[2]
         taps = k * k if kind == "conv" else 4
         self.layer_flops.append((f"{scope}/{name}", 2.0 * n * oh * ow * taps * cin * cout))
@@ -451,6 +450,36 @@ class Engine:
         which = os.environ.get("FN2_WREG_KERNELS", "false>")
         return rc == 0 and buf.value.decode().startswith("conv_igemm2_kernel") and buf.value.decode().endswith(which)
 
+    def _head_tail(self, scope, pf_name, partials, taps, ring, bias, pf, up):
+        """fn2_flow_head_tail_slabs: the taps x taps shifted partials (`partials`: _head_slabs' answer) + bias -> pf and, in
+        the same launch, the upsample_flow that follows the head (up = (layer name, destination slice) or None)."""
+        t_ptr, t_cs, nslab, slab, tscale = partials
+        n, h, wd = pf.shape[0], pf.shape[1], pf.shape[2]
+        label, uw, ub, uv = f"{scope}/{pf_name}/tail", None, None, None
+        if up is not None:
+            uw, ub, uv = self._upflow_rec(scope, up[0], pf, up[1])
+            label += "+" + up[0]
+        self._op(label, self.lib.fn2_flow_head_tail_slabs, t_ptr, t_cs, nslab, slab, C.c_float(tscale), taps,
+                 _hip.ptr(bias) if bias is not None else None, _hip.ptr(pf), n, h, wd, ring,
+                 _hip.ptr(uw) if uw is not None else None, _hip.ptr(ub) if ub is not None else None,
+                 C.byref(uv) if uv is not None else None, kernel="flow_head_tail")
+
+    def _gemm_head(self, scope, gemm_name, pf_name, src, pk, taps, ring, bias, pf, up):
+        """A flow head's interior as a 1x1 GEMM (weight pk: 2 * taps^2 outputs, (tap, o)-major) into the lane's fp32
+        scratch, then the tail.  One scratch per lane and width (32 / 64 floats per pixel): its launches are ordered."""
+        sbuf, sc0, sc = src
+        width = 32 if taps == 3 else 64
+        key = (self._branch, width)
+        if key not in self._head_t:
+            self._head_t[key] = torch.zeros((self.N * self.H * self.W, width), dtype=torch.float32, device=self.device)
+        head_t = self._head_t[key]
+        n, h, wd = pf.shape[0], pf.shape[1], pf.shape[2]
+        d = self._conv_desc(self._v(sbuf, sc, sc0),
+                            _hip.Fn2Tensor(head_t.data_ptr(), _hip.FN2_F32, n, h, wd, 2 * taps * taps, width, 0), pk)
+        self.keep.append(pk.w)
+        self._op(f"{scope}/{gemm_name}", self.lib.fn2_conv2d, C.byref(d))
+        self._head_tail(scope, pf_name, self._head_slabs(d, head_t, width), taps, ring, bias, pf, up)
+
     def _head_gemm(self, scope, spec, src, dst, up=None):
         """predict_flowN as a GEMM: 1x1 convolution with 18 outputs (tap*2 + co) on the LDS-DMA kernel into a shared
         fp32 scratch tensor, then fn2_flow_head_tail: the nine shifted partials summed AND, in the same launch, the
@@ -459,60 +488,17 @@ class Engine:
         name, kind, k, stride, pad, cin, cout, act = spec
         sbuf, sc0, sc = src
         pf = dst[0]
-        in_code = self._code(sbuf)
-        esz = 2 if in_code in (_hip.FN2_BF16, _hip.FN2_F16) else 4
-        cin_line = _round_up(cin, 128 // esz)
-        if sc0 + cin_line > sbuf.shape[3]:
-            return False
-        plan = _hip.conv_plan(in_code, cin_line, 18)
-        if plan.layout != 1:
+        if not self._cin_run(self._code(sbuf), sbuf, sc0, sc, 18)[1]:
             return False
         w = np.asarray(self._w(f"{scope}/{name}/weights"), np.float32)          # [3,3,cin,2] HWIO
         w1 = np.ascontiguousarray(w.transpose(2, 0, 1, 3)).reshape(1, 1, cin, 18)     # [ci][(ky*3+kx)*2+co]
-        packed, cin_pad, cout_pad, kpad = W.pack_conv(w1, plan.cout_tile, plan.kstep_elems, cin_line, plan.layout)
-        out_scale = 1.0
-        if plan.wgt_dtype == _hip.FN2_F16X2:
-            wmax = float(abs(packed).max())
-            if wmax > 0:
-                k2 = int(math.floor(math.log2(1024.0 / wmax)))
-                packed, out_scale = packed * (2.0 ** k2), 2.0 ** (-k2)
-        wdev = W.packed_to_device(packed, plan.wgt_dtype, self.device)
+        pk = self._pack_weight(src, w1, 18, W.pack_conv, lds_only=True)
         bias = self._bias(scope, name, kind, cout)
-        if self._head_t is None:
-            self._head_t = {}
-        if self._branch not in self._head_t:  # one scratch for every head of a branch: its launches are ordered
-            self._head_t[self._branch] = torch.zeros((self.N * self.H * self.W, 32), dtype=torch.float32, device=self.device)
-        head_t = self._head_t[self._branch]
+        self.keep.append(bias)
+        self._gemm_head(scope, name, name, src, pk, 3, 0, bias, pf,
+                        up if int(os.environ.get("FN2_FUSE_UPFLOW", "1")) else None)
         n, h, wd = pf.shape[0], pf.shape[1], pf.shape[2]
-        d = _hip.Fn2ConvDesc()
-        d.inp = self._v(sbuf, sc, sc0)
-        d.out = _hip.Fn2Tensor(head_t.data_ptr(), _hip.FN2_F32, n, h, wd, 18, 32, 0)
-        d.wgt, d.bias = wdev.data_ptr(), None
-        d.kind, d.kh, d.kw, d.stride, d.pad = 0, 1, 1, 1, 0
-        d.act = _hip.ACT_NONE
-        d.cin_pad, d.cout_pad, d.kpad, d.wgt_layout = cin_pad, cout_pad, kpad, plan.layout
-        d.out_scale = out_scale
-        self.keep += [d, wdev, bias]
-        self.conv_descs.append(d)
-        self.desc_branch.append(self._branch)
-        tn = _TNAME[self.dtype_name] if in_code == self.act_code else "float"
-        self._op(f"{scope}/{name}", self.lib.fn2_conv2d, C.byref(d),
-                 kernel=f"conv_igemm2_kernel<{tn}, float, {conv2_kernel_args(plan.cout_tile, 0, cout_pad, 1, tn == 'fn2::x2_t')}>")
-        t_ptr, t_cs, nslab, slab, tscale = self._head_slabs(d, head_t, 32)
-        if up is not None and int(os.environ.get("FN2_FUSE_UPFLOW", "1")):
-            up_name, (ubuf, uc0, uc) = up
-            uw = W.to_device(self._w(f"{scope}/{up_name}/weights"), torch.float32, self.device)  # [4,4,2,2] HW-O-I
-            ub = self._bias(scope, up_name, "deconv", 2)  # only the fusion net's two (flownet2.py:70-73, :86-89)
-            uv = self._v(ubuf, uc, uc0)
-            self.keep += [uw, ub, uv]
-            self.layers.append(dict(scope=scope, name=up_name, kind="upflow", src=pf, dst=up[1], w=uw, b=ub, view=uv))
-            self._op(f"{scope}/{name}/tail+{up_name}", self.lib.fn2_flow_head_tail_slabs, t_ptr, t_cs, nslab, slab,
-                     C.c_float(tscale), 3, _hip.ptr(bias) if bias is not None else None, _hip.ptr(pf), n, h, wd, 0, _hip.ptr(uw),
-                     _hip.ptr(ub) if ub is not None else None, C.byref(uv), kernel="flow_head_tail")
-        else:
-            self._op(f"{scope}/{name}/tail", self.lib.fn2_flow_head_tail_slabs, t_ptr, t_cs, nslab, slab, C.c_float(tscale), 3,
-                     _hip.ptr(bias) if bias is not None else None, _hip.ptr(pf), n, h, wd, 0, None, None, None,
-                     kernel="flow_head_tail")
+        esz = 2 if self._code(sbuf) in (_hip.FN2_BF16, _hip.FN2_F16) else 4
         self.layer_flops.append((f"{scope}/{name}", 2.0 * n * h * wd * 9 * cin * 2))
         self.layer_io_bytes.append((f"{scope}/{name}", float(n * h * wd * (cin * esz + 2 * 4) + 18 * cin * esz)))
         return True
@@ -530,11 +516,7 @@ class Engine:
         in_code = self._code(sbuf)
         if in_code != _hip.FN2_F16X2 or sc0 % 8 or sbuf.shape[1] < 3 or sbuf.shape[2] < 3:
             return False
-        cin_line = _round_up(sc, 32)
-        if sc0 + cin_line > sbuf.shape[3]:
-            return False
-        plan = _hip.conv_plan(in_code, cin_line, 50)
-        if plan.layout != 1:
+        if not self._cin_run(in_code, sbuf, sc0, sc, 50)[1]:
             return False
         ic_name, pf_name = ic_spec[0], pf_spec[0]
         w1, w2 = self._w(f"{scope}/{ic_name}/weights"), self._w(f"{scope}/{pf_name}/weights")
@@ -549,69 +531,25 @@ class Engine:
         wcd = W.to_device(wc, torch.float32, self.device)
         bcd = W.to_device(bias5.astype(np.float32), torch.float32, self.device)
         vin = self._v(sbuf, sc, sc0)
-        self.keep += [wcd, bcd, vin]
         # ---- interior: 1x1 GEMM with 50 outputs (tap * 2 + o), then the 25-tap tail
         w1x1 = np.ascontiguousarray(w5[4].transpose(2, 0, 1, 3)).reshape(1, 1, sc, 50).astype(np.float32)
-        packed, cin_pad, cout_pad, kpad = W.pack_conv(w1x1, plan.cout_tile, plan.kstep_elems, cin_line, plan.layout)
-        out_scale = 1.0
-        wmax = float(abs(packed).max())
-        if wmax > 0:
-            k2 = int(math.floor(math.log2(1024.0 / wmax)))
-            packed, out_scale = packed * (2.0 ** k2), 2.0 ** (-k2)
-        wdev = W.packed_to_device(packed, plan.wgt_dtype, self.device)
-        cm = ic_spec[6]
-        if n * h * wd >= int(os.environ.get("FN2_HEAD5_MIN", "65536")) and plan.cout_tile == 64 and kpad == cin_pad:
-            # large maps: GEMM and tail in one launch, the partials stay in LDS (fn2_flow_head5); the upsample_flow that
-            # follows is then its own launch (the caller's)
-            b5 = W.to_device(bias5[4].astype(np.float32), torch.float32, self.device)
-            vx = self._v(sbuf, sc, sc0)
-            self.keep += [wdev, b5, vx]
-            strip = cin_pad in (96, 192) and int(os.environ.get("FN2_H5_STRIP", "1"))   # conv.hip: fn2_flow_head5
-            self._op(f"{scope}/{ic_name}+{pf_name}", self.lib.fn2_flow_head5, C.byref(vx), _hip.ptr(wdev), cin_pad, kpad,
-                     C.c_float(out_scale), _hip.ptr(b5), _hip.ptr(pf), 1, _hip.ptr(wcd), _hip.ptr(bcd),
-                     kernel=("head5_strip_kernel<%d>" % (cin_pad // 96)) if strip else
-                     "conv_igemm2_kernel<fn2::x2_t, float, 1, 4, 2, 2, 2, 1, false, false, false, true>")
-            self.layer_flops.append((f"{scope}/{ic_name}+{pf_name}", 2.0 * n * h * wd * 9 * (sc * cm + cm * 2)))
-            self.layer_io_bytes.append((f"{scope}/{ic_name}+{pf_name}", float(n * h * wd * (sc * 4 + 2 * 4) + 9 * (sc * cm + 2 * cm) * 4)))
-            return 1
-        self._op(f"{scope}/{pf_name}/ring", self.lib.fn2_flow_head_ring, C.byref(vin), _hip.ptr(wcd), _hip.ptr(bcd), _hip.ptr(pf),
-                 kernel="flow_head_ring")
-        if self._head_t is None:
-            self._head_t = {}
-        key = (self._branch, 64)
-        if key not in self._head_t:
-            self._head_t[key] = torch.zeros((self.N * self.H * self.W, 64), dtype=torch.float32, device=self.device)
-        head_t = self._head_t[key]
-        d = _hip.Fn2ConvDesc()
-        d.inp = self._v(sbuf, sc, sc0)
-        d.out = _hip.Fn2Tensor(head_t.data_ptr(), _hip.FN2_F32, n, h, wd, 50, 64, 0)
-        d.wgt, d.bias = wdev.data_ptr(), None
-        d.kind, d.kh, d.kw, d.stride, d.pad = 0, 1, 1, 1, 0
-        d.act = _hip.ACT_NONE
-        d.cin_pad, d.cout_pad, d.kpad, d.wgt_layout = cin_pad, cout_pad, kpad, plan.layout
-        d.out_scale = out_scale
+        pk = self._pack_weight(src, w1x1, 50, W.pack_conv, lds_only=True)
         b5 = W.to_device(bias5[4].astype(np.float32), torch.float32, self.device)
-        self.keep += [d, wdev, b5]
-        self.conv_descs.append(d)
-        self.desc_branch.append(self._branch)
-        self._op(f"{scope}/{ic_name}+{pf_name}", self.lib.fn2_conv2d, C.byref(d), kernel="conv_igemm2_kernel (composed head)")
-        t_ptr, t_cs, nslab, slab, tscale = self._head_slabs(d, head_t, 64)
-        if up is not None:
-            up_name, (ubuf, uc0, uc) = up
-            uw = W.to_device(self._w(f"{scope}/{up_name}/weights"), torch.float32, self.device)
-            ub = self._bias(scope, up_name, "deconv", 2)
-            uv = self._v(ubuf, uc, uc0)
-            self.keep += [uw, ub, uv]
-            self.layers.append(dict(scope=scope, name=up_name, kind="upflow", src=pf, dst=up[1], w=uw, b=ub, view=uv))
-            self._op(f"{scope}/{pf_name}/tail+{up_name}", self.lib.fn2_flow_head_tail_slabs, t_ptr, t_cs, nslab, slab,
-                     C.c_float(tscale), 5, _hip.ptr(b5), _hip.ptr(pf), n, h, wd, 1, _hip.ptr(uw),
-                     _hip.ptr(ub) if ub is not None else None, C.byref(uv), kernel="flow_head_tail")
-        else:
-            self._op(f"{scope}/{pf_name}/tail", self.lib.fn2_flow_head_tail_slabs, t_ptr, t_cs, nslab, slab, C.c_float(tscale), 5,
-                     _hip.ptr(b5), _hip.ptr(pf), n, h, wd, 1, None, None, None, kernel="flow_head_tail")
+        self.keep += [wcd, bcd, vin, b5]
+        cm = ic_spec[6]
         # algorithmic work = what the reference graph does (two 3x3 convolutions), whatever form executes it
         self.layer_flops.append((f"{scope}/{ic_name}+{pf_name}", 2.0 * n * h * wd * 9 * (sc * cm + cm * 2)))
         self.layer_io_bytes.append((f"{scope}/{ic_name}+{pf_name}", float(n * h * wd * (sc * 4 + 2 * 4) + 9 * (sc * cm + 2 * cm) * 4)))
+        if n * h * wd >= int(os.environ.get("FN2_HEAD5_MIN", "65536")) and pk.tile == 64 and pk.kpad == pk.cin_pad:
+            # large maps: GEMM and tail in one launch, the partials stay in LDS (fn2_flow_head5: strip or tile form, the
+            # library's choice); the upsample_flow that follows is then its own launch (the caller's)
+            self.keep.append(pk.w)
+            self._op(f"{scope}/{ic_name}+{pf_name}", self.lib.fn2_flow_head5, C.byref(vin), _hip.ptr(pk.w), pk.cin_pad, pk.kpad,
+                     C.c_float(pk.out_scale), _hip.ptr(b5), _hip.ptr(pf), 1, _hip.ptr(wcd), _hip.ptr(bcd))
+            return 1
+        self._op(f"{scope}/{pf_name}/ring", self.lib.fn2_flow_head_ring, C.byref(vin), _hip.ptr(wcd), _hip.ptr(bcd), _hip.ptr(pf),
+                 kernel="flow_head_ring")
+        self._gemm_head(scope, f"{ic_name}+{pf_name}", pf_name, src, pk, 5, 1, b5, pf, up)
         return 2 if up is not None else 1
 
     def _conv_stem(self, scope, spec, sbuf, dst, s2d=False):
@@ -633,53 +571,22 @@ class Engine:
                     w[ky // 2, kx // 2, ((ky & 1) * 2 + (kx & 1)) * 4:((ky & 1) * 2 + (kx & 1)) * 4 + 3] = w_hwio[ky, kx]
             w_hwio, k, stride, cin = w, k2, 1, 16
         cs = sbuf.shape[3]
-        in_code = self._code(sbuf)
-        esz = 2 if in_code in (_hip.FN2_BF16, _hip.FN2_F16) else 4
-        run = _round_up(k * cs, 128 // esz)
-        plan = _hip.conv_plan(in_code, run, cout)
-        assert plan.layout == 1, (scope, name)
-        packed, cin_pad, cout_pad, kpad = W.pack_stem(w_hwio, cs, run, plan.cout_tile, plan.layout)
+        esz = 2 if self._code(sbuf) in (_hip.FN2_BF16, _hip.FN2_F16) else 4
         bias = self._bias(scope, name, kind, cout)
-        out_scale = 1.0
-        if plan.wgt_dtype == _hip.FN2_F16X2:
-            k2 = int(math.floor(math.log2(1024.0 / float(abs(packed).max()))))
-            packed, out_scale = packed * (2.0 ** k2), 2.0 ** (-k2)
-        wdev = W.packed_to_device(packed, plan.wgt_dtype, self.device)
-        d = _hip.Fn2ConvDesc()
-        d.inp = self._v(sbuf, cs, 0)
-        d.out = self._v(dbuf, dc, dc0)
-        d.wgt = wdev.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.kind = 2
-        d.kh = d.kw = k
-        d.stride, d.pad = stride, 0
-        d.act = _hip.ACT_LEAKY if act else _hip.ACT_NONE
-        d.cin_pad, d.cout_pad, d.kpad = cin_pad, cout_pad, kpad
-        d.wgt_layout = plan.layout
-        d.out_scale = out_scale
-        self.keep += [d, wdev, bias]
-        self.conv_descs.append(d)
-        self.desc_branch.append(self._branch)
+        d, pk = self._packed_conv((sbuf, 0, cs), dst, w_hwio, lambda w, tile, kstep, run, layout: W.pack_stem(w, cs, run, tile, layout),
+                                  2, k, stride, 0, act, bias, cin_pad=_round_up(k * cs, 128 // esz))
+        assert pk.layout == 1, (scope, name)
         self.layers.append(dict(scope=scope, name=name, kind=2, k=k, stride=stride, pad=pad, cin=cin, cout=cout,
-                                act=bool(act), src=(sbuf, 0, cs), dst=dst, desc=d, w=wdev, b=bias, cin_pad=cin_pad,
-                                cout_pad=cout_pad, kpad=kpad, layout=plan.layout, tile=plan.cout_tile,
-                                kstep=plan.kstep_elems, cs=cs))
-        tn = _TNAME[self.dtype_name]
-        self._op(f"{scope}/{name}", self.lib.fn2_conv2d, C.byref(d),
-                 kernel=f"conv_igemm2_kernel<{tn}, {tn}, {conv2_kernel_args(plan.cout_tile, 0, cout_pad, 1, tn == 'fn2::x2_t')}>")
+                                act=bool(act), src=(sbuf, 0, cs), dst=dst, desc=d, b=bias, cs=cs, **self._layer_facts(pk)))
+        self._op(f"{scope}/{name}", self.lib.fn2_conv2d, C.byref(d))
         n, oh, ow = dbuf.shape[0], dbuf.shape[1], dbuf.shape[2]
         self.layer_flops.append((f"{scope}/{name}", 2.0 * n * oh * ow * k_alg * k_alg * cin_alg * cout))
         self.layer_io_bytes.append((f"{scope}/{name}", float(sbuf.numel() * esz + n * oh * ow * cout * esz
                                                             + k_alg * k_alg * cin_alg * cout * esz)))
 
     def _upflow(self, scope, name, src_f32, dst):
-        dbuf, dc0, dc = dst
-        w = W.to_device(self._w(f"{scope}/{name}/weights"), torch.float32, self.device)  # [4,4,2,2] HW-O-I
-        b = self._bias(scope, name, "deconv", 2)  # only the fusion net's two (flownet2.py:70-73, :86-89)
-        v = self._v(dbuf, dc, dc0)
-        self.keep += [w, v, b]
+        w, b, v = self._upflow_rec(scope, name, src_f32, dst)
         n, h, wd, _ = src_f32.shape
-        self.layers.append(dict(scope=scope, name=name, kind="upflow", src=src_f32, dst=dst, w=w, b=b, view=v))
         self._op(f"{scope}/{name}", self.lib.fn2_upsample_flow, _hip.ptr(src_f32), _hip.ptr(w),
                  _hip.ptr(b) if b is not None else None, C.byref(v), n, h, wd)
 
@@ -690,19 +597,37 @@ class Engine:
                  self.W, C.c_float(scale))
         return dst
 
-    def _resolve_kernel_names(self):
-        """Ask the library which instantiation each fn2_conv2d launch takes (tile, ring, K groups, halo: decided in
-        conv.hip / conv2.hip from the geometry, the workspace and the tuning knobs) -- the per-kernel tables of the
-        bench and the PMC traffic lookup then carry the names rocprofv3 reports."""
+    def kernel_name(self, fn, args):
+        """The device kernel (template instantiation, as rocprofv3 prints it) the library launches for fn(*args, stream),
+        for the three entries that choose among instantiations -- the choice (tile, ring, K groups, fragment order,
+        halo, row-run, stem, strip; from the geometry, the workspace and the tuning knobs) is made in conv.hip / conv2.hip
+        / corr.hip and asked there, host-only.  None for any other entry; a refused query raises."""
+        lib = self.lib
+        if fn is lib.fn2_conv2d:
+            query, qargs = lib.fn2_conv2d_kernel_name, args
+        elif fn is lib.fn2_correlation_fused:
+            query, qargs = lib.fn2_correlation_fused_kernel_name, args[:5]   # (without the activation)
+        elif fn is lib.fn2_flow_head5:
+            query, qargs = lib.fn2_flow_head5_kernel_name, args
+        else:
+            return None
         buf = C.create_string_buffer(256)
+        _hip.check(query(*qargs, buf, 256))
+        assert buf.value, fn.__name__
+        return buf.value.decode()
+
+    def _resolve_kernel_names(self):
+        """The single place that names launches: the per-kernel tables of the bench and the PMC traffic lookup carry the
+        names rocprofv3 reports.  Runs behind _alloc_workspace (the split-K decision depends on the workspace)."""
         for i, (name, fn, args) in enumerate(self.ops):
-            if fn is self.lib.fn2_conv2d:
-                if self.lib.fn2_conv2d_kernel_name(args[0], buf, 256) == 0 and buf.value:
-                    self.kernel_of[i] = buf.value.decode()
+            try:
+                self.kernel_of[i] = self.kernel_name(fn, args) or self.kernel_of[i]
+            except Exception as e:
+                raise type(e)("%s: %s" % (name, e)) from None
 
     def _alloc_workspace(self):
         """One fp32 split-K scratch buffer per branch, shared by the branch's layers (its launches are ordered)."""
-        branches = self.desc_branch + [0] * (len(self.conv_descs) - len(self.desc_branch))  # the trainer appends descs
+        branches = self.desc_branch   # (parallel to conv_descs: _conv_desc registers both, the trainer's descriptors too)
         self.workspace = {}
         for br in sorted(set(branches)):
             descs = [d for d, b in zip(self.conv_descs, branches) if b == br and C.addressof(d) not in self._own_ws]
@@ -877,9 +802,8 @@ class Engine:
         net = self._buf(f"{tag}/corr_concat", N, H // 8, W_ // 8, 473)  # [conv_redir(32) | corr(441)], :46
         va, vb, vo = self._v(c3a, 256, 0), self._v(c3b, 256, 0), self._v(net, 441, 32)
         self.keep += [va, vb, vo]
-        tn = _TNAME[self.dtype_name]
         self._op(f"{tag}/correlation", self.lib.fn2_correlation_fused, C.byref(va), C.byref(vb), C.byref(vo), 20, 2,
-                 _hip.ACT_LEAKY, kernel=self._corr_kernel_name(tn, H // 8))  # correlation(a3, b3, 1, 20, 1, 2, 20) + LeakyReLU, :40-41
+                 _hip.ACT_LEAKY)  # correlation(a3, b3, 1, 20, 1, 2, 20) + LeakyReLU, :40-41
         # pseudo-layer for the trainer: the cost volume has no parameters but passes gradients to both towers
         self.layers.append(dict(scope=scope, name="correlation", kind="corr", fa=c3a, fb=c3b, dst=(net, 32, 441)))
         self.layer_flops.append((f"{scope}/correlation", 2.0 * N * (H // 8) * (W_ // 8) * 441 * 256))
@@ -914,14 +838,6 @@ class Engine:
         c6_1 = self._encoder_tail(scope, tag, L, cats)
         preds = self._refine(scope, tag, L, c6_1, cats, True)
         return self._final_flow(tag, preds, 0.05)  # flownet_sd.py:106-110
-
-    def _corr_kernel_name(self, tn, h):
-        """Device kernel fn2_correlation_fused picks (corr.hip): corr3 (same-parity row pairs) for 16-bit / split-fp16
-        features when the feature height is a multiple of 4, else corr2."""
-        nl = 4 if self.dtype_name in ("bf16", "f16") else 8
-        if self.dtype_name != "f32" and h % 4 == 0 and int(os.environ.get("FN2_CORR3", "1")):
-            return f"corr3_kernel<{tn}, {tn}, {nl}>"
-        return f"corr2_kernel<{tn}, {tn}, {nl}>"
 
     def _pair_input(self, tag, pad):
         """[a | b] with the stem's zero border of `pad` pixels baked in (flownet_s.py:24,39)."""

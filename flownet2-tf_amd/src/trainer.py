@@ -19,6 +19,7 @@ copies that the input-gradient convolutions read are refreshed once per step by 
 import ctypes as C
 import math
 import os
+import types
 
 import numpy as np
 import torch
@@ -309,8 +310,8 @@ class FlowNetSTrainer:
         sbuf, sc0, sc = rec["src"]
         pf = rec["dst"][0]
         code = eng._code(sbuf)
-        line = _round_up(sc, 32)
-        if sc0 + line > sbuf.shape[3] or _hip.conv_plan(code, line, 18).layout != 1:
+        line, whole = eng._cin_run(code, sbuf, sc0, sc, 18)
+        if not whole:
             return False
         plan = _hip.conv_plan(code, line, 18)
         idx = np.zeros((1, 1, sc, 18), np.float64)
@@ -320,20 +321,13 @@ class FlowNetSTrainer:
         pk, cin_pad, cout_pad, kpad = W.pack_conv(idx + 1.0, plan.cout_tile, plan.kstep_elems, line, plan.layout, dtype=np.float64)
         gmap = torch.from_numpy((pk.reshape(-1) - 1.0).astype(np.int32)).to(self.dev)
         wf = torch.zeros(gmap.numel(), dtype=torch.float32, device=self.dev)  # split fp16 in an fp32 container
-        wmax = float(rec["master"].abs().max().item())
-        scale = 2.0 ** int(math.floor(math.log2(1024.0 / wmax))) if wmax > 0 else 1.0
-        self.gathers.append([wf, rec["master"], gmap, scale, 0])
+        out_scale = W.scale_f16x2(rec["master"].detach().cpu().numpy())[1]   # (the gather applies 1 / out_scale every step)
+        self.gathers.append([wf, rec["master"], gmap, 1.0 / out_scale, 0])
         n, h, w = int(pf.shape[0]), int(pf.shape[1]), int(pf.shape[2])
         t18 = torch.zeros((n * h * w, 32), dtype=torch.float32, device=self.dev)
-        d = _hip.Fn2ConvDesc()
-        d.inp = self._view(sbuf, sc, sc0)
-        d.out = _hip.Fn2Tensor(t18.data_ptr(), _hip.FN2_F32, n, h, w, 18, 32, 0)
-        d.wgt, d.bias = wf.data_ptr(), None
-        d.kind, d.kh, d.kw, d.stride, d.pad = 0, 1, 1, 1, 0
-        d.act = _hip.ACT_NONE
-        d.cin_pad, d.cout_pad, d.kpad, d.wgt_layout = cin_pad, cout_pad, kpad, plan.layout
-        d.out_scale = 1.0 / scale
-        eng.conv_descs.append(d)
+        d = eng._conv_desc(self._view(sbuf, sc, sc0), _hip.Fn2Tensor(t18.data_ptr(), _hip.FN2_F32, n, h, w, 18, 32, 0),
+                           types.SimpleNamespace(w=wf, cin_pad=cin_pad, cout_pad=cout_pad, kpad=kpad, layout=plan.layout,
+                                                 out_scale=out_scale), lane=0)
         bias = _hip.ptr(rec["b"]) if rec.get("b") is not None else None
         self.keep += [d, wf, gmap, t18]
 
@@ -453,12 +447,8 @@ class FlowNetSTrainer:
         gy_buf, gy_c0, gy_c = g_src
         gx_buf, gx_c0, gx_c = g_dst
         cin_b, cout_b = gy_c, gx_c
-        code = self.code
-        cin_pad = _round_up(cin_b, 8)
-        line = _round_up(cin_b, 32)
-        if gy_c0 + line <= gy_buf.shape[3] and _hip.conv_plan(code, line, cout_b).layout == 1:
-            cin_pad = line
-        plan = _hip.conv_plan(code, cin_pad, cout_b)
+        cin_pad = self.eng._cin_run(self.code, gy_buf, gy_c0, cin_b, cout_b)[0]
+        plan = _hip.conv_plan(self.code, cin_pad, cout_b)
         enum = hwio_index.astype(np.float64) + 1.0
         if kind == 3:
             pk, cin_pad, cout_pad, kpad = W.pack_conv_transpose_s2(enum, pad, plan.cout_tile, plan.kstep_elems, cin_pad,
@@ -471,29 +461,14 @@ class FlowNetSTrainer:
         scale = rec.get("scale", 1.0)
         gather = [wb, rec["master"], gmap, scale, 0]   # (last: packed row length when the copy is in fragment order)
         self.gathers.append(gather)
-        d = _hip.Fn2ConvDesc()
-        d.inp = self._view(gy_buf, gy_c, gy_c0)
-        d.out = self._view(gx_buf, gx_c, gx_c0)
-        d.wgt, d.bias = wb.data_ptr(), None
-        d.kind, d.kh, d.kw, d.stride, d.pad = kind, k, k, stride, pad
-        d.act = _hip.ACT_NONE
-        d.cin_pad, d.cout_pad, d.kpad, d.wgt_layout = cin_pad, cout_pad, kpad, plan.layout
-        d.accumulate = 1
-        d.out_scale = 1.0 / scale
+        # (registered on lane 0 with the engine's descriptors: shares the split-K workspace)
+        d = self.eng._conv_desc(self._view(gy_buf, gy_c, gy_c0), self._view(gx_buf, gx_c, gx_c0),
+                                types.SimpleNamespace(w=wb, cin_pad=cin_pad, cout_pad=cout_pad, kpad=kpad, layout=plan.layout,
+                                                      out_scale=1.0 / scale),
+                                kind, k, stride, pad, accumulate=True, lane=0)
         if self.eng.fragment_weights and plan.layout == 1 and plan.cout_tile == 128 and self.eng._wants_fragments(d):
             d.wgt_layout, gather[4] = 2, kpad   # the gather writes this copy in MFMA-fragment order
         self.keep += [d, wb, gmap]
-        self.eng.conv_descs.append(d)  # shares the split-K workspace
-        tn = "fn2::x2_t" if self.x2 else "float"
-        if plan.layout == 1:
-            from .engine import conv2_kernel_args
-            gxs = gx_buf.shape
-            m_px = gxs[0] * gxs[1] * gxs[2] // (4 if kind == 3 else 1)
-            d.kernel_name = "conv_igemm2_kernel<%s, %s, %s>" % (tn, tn, conv2_kernel_args(plan.cout_tile, m_px, cout_pad,
-                                                                                               4 if kind == 3 else 1, self.x2))
-        else:
-            d.kernel_name = "conv_igemm_kernel<float, float, %s>" % {128: "4, 2, 2", 64: "4, 1, 4", 32: "2, 1, 4",
-                                                                      16: "1, 1, 4"}[plan.cout_tile]
         return d
 
     def _plan_conv(self, rec):
@@ -630,9 +605,7 @@ class FlowNetSTrainer:
             for fn, args in ops:
                 fl, kern = 0.0, fn.__name__.replace("fn2_", "") + "_kernel"
                 if fn is self.lib.fn2_conv2d:
-                    buf = C.create_string_buffer(256)  # the instantiation the library takes (tile, ring, fragment order, split)
-                    rc = self.lib.fn2_conv2d_kernel_name(args[0], buf, 256)
-                    fl, kern = flops.get(name, 0.0), (buf.value.decode() if rc == 0 and buf.value else args[0]._obj.kernel_name)
+                    fl, kern = flops.get(name, 0.0), self.eng.kernel_name(fn, args)   # (tile, ring, fragment order, split)
                 elif fn is self.lib.fn2_conv2d_bwd_filter:
                     fl, kern = flops.get(name, 0.0), ("bwd_filter_x2_kernel" if self.x2 else "bwd_filter_kernel")
                 out.append(("bwd " + name, fn, args, kern, fl))

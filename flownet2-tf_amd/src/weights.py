@@ -6,6 +6,7 @@ use seeded variance-scaling weights; real weights converted by the reference's
 scripts/caffe/convert_caffe_weights_to_npy.py (HWIO / HW-O-I, names
 ``<scope>/<layer>/weights|biases``) load through ``load_npz`` unchanged.
 """
+import math
 import os
 
 import numpy as np
@@ -236,6 +237,17 @@ def split_f16x2(packed):
     hi = g.astype(np.float16)
     lo = (g - hi.astype(np.float32)).astype(np.float16)
     return np.stack([hi, lo], axis=-2).reshape(p.shape[:-1] + (2 * p.shape[-1],))
+
+
+def scale_f16x2(packed):
+    """Power-of-two scaling of a weight that is stored as split fp16: (packed * 2^k, 2^-k) with max|w| * 2^k in
+    (512, 1024], so that the lo parts stay normal fp16 numbers over 4 decades of weight magnitude; the kernel multiplies
+    its accumulator by out_scale = 2^-k.  Both factors are exact.  An all-zero weight is left as it is (scale 1)."""
+    wmax = float(np.abs(packed).max())
+    if not wmax > 0:
+        return packed, 1.0
+    k2 = int(math.floor(math.log2(1024.0 / wmax)))
+    return packed * (2.0 ** k2), 2.0 ** (-k2)
 
 
 def join_f16x2(split):

@@ -240,10 +240,14 @@ int fn2_conv2d_plan(int in_dtype, int cin_pad, int cout, fn2_conv_plan* plan);
  * one buffer of the maximum over layers can be shared by all launches on a stream. */
 int64_t fn2_conv2d_workspace_bytes(const fn2_conv_desc* d);
 int fn2_conv2d(const fn2_conv_desc* d, void* stream);
-/* The device kernel (template instantiation, as rocprofv3 prints it without "void fn2::" and the argument list) that
- * fn2_conv2d would launch for this descriptor under the current tuning knobs -- the tile / ring / K-group / halo choice is
- * made inside the library; profiles and the bench's per-kernel table name launches by it.  "" for the paths that do
- * not report (generic kernel, flow heads).  Launches nothing. */
+/* Host-only: the device kernel (template instantiation, as rocprofv3 prints it without "void fn2::", the argument list
+ * and the defaulted trailing template arguments: a prefix of the profiler's row) that fn2_conv2d would launch for this descriptor under the current tuning knobs -- the tile / ring / K-group /
+ * halo choice is made inside the library; profiles and the bench's per-kernel table name launches by it.  Every path
+ * reports: the LDS-DMA kernels, the generic "conv_igemm_kernel<T, OutT, ..>" and "flow_head_kernel<T>"; an accepted
+ * descriptor never yields "".  It walks fn2_conv2d itself up to the launch site, so it runs the same checks and returns
+ * the same refusals (the name is then ""); it launches nothing, calls no HIP runtime function and never dereferences
+ * the data pointers.  A riding head (desc.head) and the split-K finalize pass are not named: the name is that of the
+ * convolution's own launch. */
 int fn2_conv2d_kernel_name(const fn2_conv_desc* desc, char* name, int cap);
 /* Number of K splits fn2_conv2d(desc) takes with desc's workspace (1 = no split-K: no slabs, no finalize pass). */
 int fn2_conv2d_splits(const fn2_conv_desc* desc);
@@ -284,6 +288,12 @@ int fn2_flow_head_tail_slabs(const float* t, int t_cs, int nslab, int64_t slab_s
  * with ring_w == NULL they are left as they are (written by fn2_flow_head_ring, or not needed). */
 int fn2_flow_head5(const fn2_tensor* x, const void* wgt, int cin_pad, int kpad, float out_scale, const float* bias, float* pf,
                    int ring, const float* ring_w, const float* ring_b, void* stream);
+/* Host-only: the kernel that call launches -- "head5_strip_kernel<1>" / "head5_strip_kernel<2>" (cin_pad 96 / 192) or the
+ * tile form "conv_igemm2_kernel<fn2::x2_t, float, 1, 4, 2, 2, 2, 1, false, false, false, true>" (the form of
+ * fn2_conv2d_kernel_name).  One function serves both entries: same checks, same strip-or-tile decision (FN2_H5_STRIP,
+ * FN2_H5_DBG), same return codes; launches nothing and never dereferences the pointers. */
+int fn2_flow_head5_kernel_name(const fn2_tensor* x, const void* wgt, int cin_pad, int kpad, float out_scale, const float* bias,
+                               float* pf, int ring, const float* ring_w, const float* ring_b, char* name, int cap);
 /* Border ring of a composed head: pf[n,y,x,o] = bc[case][o] + sum_{u in 5x5} sum_ci wc[case][u][ci][o] x[n, y+uy-2, x+ux-2, ci]
  * for the pixels with y in {0, h-1} or x in {0, w-1}; case = 3*cy + cx with c = 0 / 1 / 2 for the low border / interior /
  * high border of that axis.  x: split-fp16 view; wc: fp32 [9][25][8*ceil(c/8)][2], zero on the pad channels; bc: fp32 [9][2]. */

@@ -179,19 +179,25 @@ def test_op_surface_dispatch_table(corr3_env, monkeypatch):
 @pytest.mark.parametrize("h", [47, 48])
 @pytest.mark.parametrize("dtype_name", DTYPES)
 def test_engine_reports_the_kernel_the_library_picks(dtype_name, h, corr3_env, monkeypatch):
-    """Engine._corr_kernel_name (its profile rows; engine.py is not part of this check's subject) against the query for the
-    engine's call: C = 256 features, the 441 channels behind conv_redir's 32 in the concat buffer, same-type output."""
-    import types
-    from src.engine import Engine, _TNAME
+    """The engine names its correlation launch by this query on the launch's own arguments (Engine.kernel_name); for
+    the engine's call shape -- C = 256 features, the 441 channels behind conv_redir's 32 in the concat buffer, same-type
+    output -- the library's answer is the documented rule's."""
     if corr3_env is None:
         monkeypatch.delenv("FN2_CORR3", raising=False)
     else:
         monkeypatch.setenv("FN2_CORR3", corr3_env)
-    stub = types.SimpleNamespace(dtype_name=dtype_name)
     cs = 512 if dtype_name in ("bf16", "f16") else 480  # Engine._buf: the 473 channels rounded up to whole 128-byte lines
     a, b = _tensor(dtype_name, 4, h, 64, 256), _tensor(dtype_name, 4, h, 64, 256)
     out = _tensor(dtype_name, 4, h, 64, 441, cs, 32)
-    assert _fused_query(a, b, out, 20, 2) == (OK, Engine._corr_kernel_name(stub, _TNAME[dtype_name], h))
+    want = expected_fused(dtype_name, 256, h, 20, 2, dtype_name, cs, 32, corr3_env is None)
+    assert want[0] == OK and want[1].startswith("corr3_kernel" if (corr3_env is None and dtype_name != "f32" and h == 48)
+                                                else "corr2_kernel")
+    assert _fused_query(a, b, out, 20, 2) == want
+    import types
+    from src.engine import Engine
+    _hip, lib = _lib()
+    launch_args = (C.byref(a), C.byref(b), C.byref(out), 20, 2, _hip.ACT_LEAKY)   # Engine._net_c's op, without the stream
+    assert Engine.kernel_name(types.SimpleNamespace(lib=lib), lib.fn2_correlation_fused, launch_args) == want[1]
 
 
 # ---- validation of fn2_correlation_fused (dummy pointers: nothing launches) ------------------------------------------

@@ -627,3 +627,65 @@ def test_single_run_equals_the_one_line_list(input_type, refined, tmp_path):
         plain = net.test(None, p["a"], input_b_path=p["b"], out_path=str(tmp_path / "plain"), save_flo=False, **single_kw,
                          **dict(kw, variational_refinement=False))
         assert not np.array_equal(plain, single)                  # the refinement did run
+
+
+_NAME_QUERY = {"fn2_conv2d": ("fn2_conv2d_kernel_name", None), "fn2_correlation_fused": ("fn2_correlation_fused_kernel_name", 5),
+               "fn2_flow_head5": ("fn2_flow_head5_kernel_name", None)}
+
+
+def _library_names(lib, launches):
+    """[(launch name, reported kernel, the library's own answer for the launch's arguments)] of the launches whose entry
+    chooses among instantiations; `launches`: (name, fn, args, reported kernel)."""
+    import ctypes as C
+    import re
+    out = []
+    for name, fn, args, reported in launches:
+        if getattr(fn, "__name__", "") not in _NAME_QUERY:
+            continue
+        query, nargs = _NAME_QUERY[fn.__name__]
+        buf = C.create_string_buffer(256)
+        assert getattr(lib, query)(*args[:nargs], buf, 256) == 0, name
+        assert buf.value and reported == buf.value.decode(), (name, reported, buf.value)
+        assert re.match(r"^[A-Za-z_0-9]+(<[^()]*>)?$", reported), (name, reported)   # an instantiation, no placeholder text
+        out.append((name, reported, fn.__name__))
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("model,shape,dtype", [("FlowNet2", (1, 256, 256), "f16x2"), ("FlowNetC", (1, 64, 64), "f32"),
+                                               ("FlowNetC", (1, 64, 64), "bf16")])
+def test_kernel_of_is_the_librarys_answer(model, shape, dtype):
+    """Every launch of fn2_conv2d, fn2_correlation_fused and fn2_flow_head5 is named by the library's host-only query on the
+    launch's own arguments, asked behind the workspace allocation.  FlowNet2 at 256 x 256 is the smallest size whose
+    full-resolution composed head reaches FN2_HEAD5_MIN (65536 pixels: fn2_flow_head5) while the 128 x 128 level takes
+    ring + GEMM + tail; FlowNetC at 64 x 64 brings the correlation and the dot-product heads in fp32 and bf16."""
+    from src import weights as W
+    from src.engine import Engine
+    n, h, w = shape
+    eng = Engine(model, W.init_weights(model, 1234), n, h, w, dtype)
+    assert len(eng.kernel_of) == len(eng.ops)
+    named = _library_names(eng.lib, [(nm, fn, args, eng.kernel_of[i]) for i, (nm, fn, args) in enumerate(eng.ops)])
+    entries = {e for _, _, e in named}
+    if model == "FlowNet2":
+        assert entries == {"fn2_conv2d", "fn2_correlation_fused", "fn2_flow_head5"}
+        assert [k for nm, k, e in named if e == "fn2_flow_head5"] == ["head5_strip_kernel<1>"]
+        assert any(nm.endswith("predict_flow1/ring") for nm, _, _ in eng.ops)   # (the 128 x 128 level: ring + GEMM + tail)
+    else:
+        assert entries == {"fn2_conv2d", "fn2_correlation_fused"}
+        assert any(k.startswith("flow_head_kernel<") for _, k, _ in named)
+    a, b = images(n, h, w, 3)
+    eng(a, b)                       # one eager launch of the plan
+    torch.cuda.synchronize()
+    assert torch.isfinite(eng.outputs["flow"]).all()
+
+
+@pytest.mark.gpu
+def test_backward_launches_name_their_convolutions_by_the_library():
+    from src import weights as W
+    from src.trainer import FlowNetSTrainer
+    tr = FlowNetSTrainer(W.init_weights("FlowNetS", 1234), 1, 64, 64)
+    launches = tr.backward_launches()
+    assert all(len(t) == 5 for t in launches)
+    named = _library_names(tr.lib, [(nm, fn, args, kern) for nm, fn, args, kern, _ in launches])
+    assert named and {e for _, _, e in named} == {"fn2_conv2d"}
+    _library_names(tr.lib, [(nm, fn, args, tr.eng.kernel_of[i]) for i, (nm, fn, args) in enumerate(tr.eng.ops)])
