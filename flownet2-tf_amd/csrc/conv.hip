@@ -1020,7 +1020,8 @@ static int build_args(const fn2_conv_desc* d, ConvArgs* out, int* tile_out, int*
   } else if (d->kind == 5) {
     // the same transposed convolution as kind 1 for 16 / 32 output channels on split fp16 (the fusion net's fuse_deconv0 /
     // fuse_deconv1, flownet2.py:66-84): blockIdx.z = output row phase a, both column phases in one block as a 2 x 3-tap
-    // convolution with 2 Cout packed rows (weights.pack_deconv_merged)
+    // convolution with 2 Cout packed rows (weights.pack_deconv_merged); column phase b multiplies only window columns b and
+    // b + 1, the ones it has weights for (conv2.hip: launch_halo, conv_halo_kernel PT)
     FN2_REQUIRE(d->kh == 4 && d->kw == 4 && d->stride == 2, "deconv (kind 5): only k=4 s=2 crop 1");
     FN2_REQUIRE((d->out.c == 16 || d->out.c == 32) && d->in.dtype == FN2_F16X2 && d->wgt_layout == 1 && d->cout_pad == 2 * d->out.c,
                 "deconv (kind 5): 16 or 32 output channels, split-fp16 input, cout_pad = 2 Cout");

@@ -942,6 +942,45 @@ __global__ void __launch_bounds__(256 * KG + (FEED ? 256 : 0)) conv_igemm2_kerne
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// fn2_conv_desc.up_src on a kind-5 launch: upsample_flowXtoY of output pixel (n, uy, ux) into channels [up_c0, up_c0 + 2)
+// (upsample_flow_kernel's arithmetic, tap for tap; conv.hip)
+template <typename OutT>
+__device__ __forceinline__ void halo_upflow_pixel(const ConvArgs& p, OutT* out, int n, int uy, int ux) {
+  const int H2 = p.out_H >> 1, W2 = p.out_W >> 1;
+  const int a = uy & 1, b = ux & 1, y = uy >> 1, x = ux >> 1;
+  float r0 = p.up_bias ? p.up_bias[0] : 0.f, r1 = p.up_bias ? p.up_bias[1] : 0.f;
+#pragma unroll
+  for (int ty = 0; ty < 2; ++ty) {
+    const int iy = y - 1 + a + ty, ky = 3 - a - 2 * ty;
+    if (iy < 0 || iy >= H2) continue;
+#pragma unroll
+    for (int tx = 0; tx < 2; ++tx) {
+      const int ix = x - 1 + b + tx, kx = 3 - b - 2 * tx;
+      if (ix < 0 || ix >= W2) continue;
+      const float2 sv = *reinterpret_cast<const float2*>(p.up_src + (((long)n * H2 + iy) * W2 + ix) * 2);
+      const float* ww = p.up_w + (ky * 4 + kx) * 4;
+      r0 += sv.x * ww[0] + sv.y * ww[1];
+      r1 += sv.x * ww[2] + sv.y * ww[3];
+    }
+  }
+  OutT* pu = out + (((size_t)n * p.out_H + uy) * p.out_W + ux) * p.out_cs + p.up_c0;
+  if ((p.up_c0 | p.out_cs) & 1) {
+    store_elem<OutT>(pu, r0);
+    store_elem<OutT>(pu + 1, r1);
+  } else if constexpr (is_x2<OutT>::value) {   // an even pair lies in one group of 8: its hi parts and its lo parts as 4-byte stores
+    typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+    const size_t addr = reinterpret_cast<size_t>(pu);
+    _Float16* g = reinterpret_cast<_Float16*>(addr & ~size_t(31)) + ((addr & 31) >> 2);
+    const _Float16 h0 = (_Float16)r0, h1 = (_Float16)r1;
+    *reinterpret_cast<h2*>(g) = h2{h0, h1};
+    *reinterpret_cast<h2*>(g + 8) = h2{(_Float16)(r0 - (float)h0), (_Float16)(r1 - (float)h1)};
+  } else {
+    const float rr[2] = {r0, r1};
+    store_vec<OutT, 2>(pu, rr);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Halo variant for stride-1 layers (3x3 convolutions and the 2x2 phase convolutions of the transposed convs) on
 // split-fp16 operands.  In the kernel above every filter tap fetches its own copy of the tile's pixel rows, although
 // the taps kx = 0..KW-1 of one kernel row read the SAME input pixels shifted by one: a tile of BP consecutive pixels
@@ -952,18 +991,34 @@ __global__ void __launch_bounds__(256 * KG + (FEED ? 256 : 0)) conv_igemm2_kerne
 // 128 x 64 tile, -44 % for 64 x 128, -53 % for 32 x 128 (KW = 3) -- the layers with few output channels (the
 // full-resolution fusion layers, deconv2, interconvN) are bound by exactly that stream.
 // Requires: stride 1, no split-K, tiles that do not straddle image rows (OW % BP == 0).
-template <typename OutT, int WC, int WP, int TCN, int TPN, int KW>
+//
+// PT = 1 (kind 5 only; a defaulted trailing argument, left out of the reported names like the others): each
+// column phase of a merged transposed conv walks its own two columns of the 2 x 3 window.  weights.pack_deconv_merged
+// gives column phase b real weights at window columns b and b + 1 and zeros at the third, so in the all-columns walk
+// half of the (column phase, window column) products of a kernel row multiply zeros.
+//   TCN = 2 (Cout = 32): the two 32-row tiles of a wave are the two column phases; tile b skips the column it has no
+//     weights for.  Same loop, same epilogue.
+//   TCN = 1 (Cout = 16): the packed 32-row tile is split into one 16-row tile per column phase on the 16x16x32
+//     instruction, and a stage is a whole (channel block, ky): the 16 real weight rows of the four (column phase, tap)
+//     pairs -- one pair per wave, 8 KB instead of the 12 KB of three 32-row tap stages -- and the halo row, one barrier
+//     instead of three.  Fragment rows and channel groups are assigned so that every ds_read_b128 is free of bank
+//     conflicts at all three window columns (below); the outputs leave through a wave-private LDS tile as 64-byte runs.
+template <typename OutT, int WC, int WP, int TCN, int TPN, int KW, int PT = 0>
 __global__ void __launch_bounds__(256) conv_halo_kernel(const ConvArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   using T = x2_t;
   constexpr int ESZ = 4;
+  constexpr bool kPT = PT != 0;
+  constexpr bool kP16 = kPT && TCN == 1;
+  static_assert(!kPT || (KW == 3 && WC == 1 && WP == 4 && TPN == 1 && TCN <= 2), "per-phase taps: the 2 x 3 window of kind 5");
   constexpr int BC = WC * TCN * 32, BP = WP * TPN * 32;
   static_assert(WC * WP == 4, "4 waves per block");
   constexpr int NWI = BC / 32;                // weight pieces (8 rows each) per wave per tap stage
   constexpr int BROWS = BP + 8;               // BP + KW - 1 pixel rows, whole pieces
   constexpr int NBP = BROWS / 8;              // pixel pieces per (channel block, ky)
   constexpr int NBW = (NBP + 3) / 4;          // ... per wave
-  __shared__ uint4 ldsA[2][BC * 8];
+  constexpr int AROWS = kP16 ? 64 : BC;       // kP16: 4 (column phase, tap) pairs x 16 output channels
+  __shared__ uint4 ldsA[2][AROWS * 8];
   __shared__ uint4 ldsB[2][BROWS * 8];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1032,9 +1087,137 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(const ConvArgs p) {
   auto issue_A = [&](int sup, int kx, uint4* lds) {
     const int sc = sup / p.KH, ky = sup - sc * p.KH;
     const int soff = ((ky * KW + kx) * spt + sc) * 128;
+    if (kPT && kx != wave / 2 && kx != wave / 2 + 1) return;  // (TCN = 2: this wave's rows are column phase wave / 2, not read at this column)
 #pragma unroll
     for (int j = 0; j < NWI; ++j) dma16(rsrc_w, &lds[(wave * (BC / 4) + j * 8) * 8], woff[j], soff);
   };
+
+  if constexpr (kP16) {
+    // ---- Cout = 16: one 16-row tile per column phase b, window columns b and b + 1 only (16x16x32 instruction)
+    // A 16x16x32 fragment is 16 rows x 4 channel groups: lane (j = l & 15, g = l >> 4) gives row j, K group g.  A
+    // ds_read_b128 is served in 16-lane groups made of j in {0-3, 12-15} of one g and j in {4-11} of the next, and 16
+    // consecutive LDS rows with one chunk index fill the 16 (row parity, swizzled chunk) slots of the 256-byte bank row
+    // exactly once.  Two chunk indices 4 apart move a lane 8 rows on in that picture, so a group is conflict-free when
+    // each of its two row sets is closed under "+ 8 rows" -- whatever the first row, i.e. at every window column:
+    //   lane j takes fragment row pr(j) = j with bits 2 and 3 swapped for j >= 8 ({0-3, 12-15} -> rows {0-3, 8-11}),
+    //   K group g takes channel group cg(g) = (0, 2, 1, 3)[g] (neighbouring g: chunk indices 4 apart).
+    // The weight rows are stored so that fragment row pr(j) holds output channel j: D row i is channel i.
+    const int r16 = lane & 15, g16 = lane >> 4;
+    const int pr = r16 ^ ((r16 & 8) >> 1);
+    const int ch = 2 * (((g16 & 1) << 1) | (g16 >> 1));
+    // weights: wave w fetches the pair (column phase b = w >> 1, tap t = w & 1) = window column b + t, LDS rows [16 w, 16 w + 16)
+    const int wb = wave >> 1, wkx = (wave >> 1) + (wave & 1);
+    unsigned woff16[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int fr16 = j * 8 + lrow;                     // fragment row <- output channel co (pr is its own inverse)
+      const int co = fr16 ^ ((fr16 & 8) >> 1);
+      const int prow = (co & 3) + 8 * (co >> 2) + 4 * wb;  // packed row of (b, co) (weights._permute_rows64)
+      const int row = wave * 16 + fr16;
+      woff16[j] = (unsigned)(c0 + prow) * wrow_bytes + (unsigned)((lphys ^ ((row >> 1) & 7)) * 16);
+    }
+    auto issue_A16 = [&](int sup, uint4* lds) {
+      const int sc = sup / p.KH, ky = sup - sc * p.KH;
+      const int soff = ((ky * KW + wkx) * spt + sc) * 128;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) dma16(rsrc_w, &lds[(wave * 16 + j * 8) * 8], woff16[j], soff);
+    };
+    f32x4 acc16[2][2];   // [column phase b][16-pixel half sp of the wave's 32 pixels]
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int sp = 0; sp < 2; ++sp) acc16[b][sp] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto compute16 = [&](const uint4* la, const uint4* lb) {
+#if FN2_SETPRIO
+      __builtin_amdgcn_s_setprio(1);
+#endif
+      uint4 bh[KW][2], bl[KW][2];
+#pragma unroll
+      for (int kx = 0; kx < KW; ++kx)
+#pragma unroll
+        for (int sp = 0; sp < 2; ++sp) {
+          const int rb = wave * 32 + sp * 16 + pr + kx, sw = (rb >> 1) & 7;
+          bh[kx][sp] = lb[rb * 8 + (ch ^ sw)];
+          bl[kx][sp] = lb[rb * 8 + ((ch + 1) ^ sw)];
+        }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int b = c >> 1, kx = (c >> 1) + (c & 1);
+        const int ra = c * 16 + pr, sw = (ra >> 1) & 7;
+        const uint4 ah = la[ra * 8 + (ch ^ sw)], al = la[ra * 8 + ((ch + 1) ^ sw)];
+#pragma unroll
+        for (int sp = 0; sp < 2; ++sp) {
+          acc16[b][sp] = mfma_16x16x32<f16_t>(al, bh[kx][sp], acc16[b][sp]);
+          acc16[b][sp] = mfma_16x16x32<f16_t>(ah, bl[kx][sp], acc16[b][sp]);
+          acc16[b][sp] = mfma_16x16x32<f16_t>(ah, bh[kx][sp], acc16[b][sp]);
+        }
+      }
+#if FN2_SETPRIO
+      __builtin_amdgcn_s_setprio(0);
+#endif
+    };
+    issue_B(0, ldsB[0]);
+    issue_A16(0, ldsA[0]);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int sup = 0; sup < nsup; ++sup) {
+      // the next (channel block, ky) in flight under this one's MFMAs; its buffers were last read a barrier ago
+      if (sup + 1 < nsup) {
+        issue_A16(sup + 1, ldsA[(sup + 1) & 1]);
+        issue_B(sup + 1, ldsB[(sup + 1) & 1]);
+      }
+      compute16(ldsA[sup & 1], ldsB[sup & 1]);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+    // ---- epilogue: lane (j, g) holds channels [4 g, 4 g + 4) of column phase b at input pixel 16 sp + pr(j) of the wave,
+    // i.e. output pixel R = 2 (16 sp + pr) + b of the wave's 64.  Through a wave-private LDS tile (the loop ended with a
+    // barrier: the stage buffers are free) they leave as whole pixels: four lanes store the 64 bytes of one.
+    OutT* out = reinterpret_cast<OutT*>(p.out);
+    constexpr int ERB = 80;   // bytes per tile row: 16 channels + 16 bytes of padding
+    static_assert(sizeof(ldsB) >= 4 * 64 * ERB, "epilogue tiles fit the pixel stage buffers");
+    char* const etl = reinterpret_cast<char*>(&ldsB[0][0]) + wave * (64 * ERB);
+    float bias[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bias[i] = p.bias != nullptr ? p.bias[4 * g16 + i] : 0.f;
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int sp = 0; sp < 2; ++sp) {
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          v[i] = acc16[b][sp][i] * p.out_scale + bias[i];
+          if (p.act == FN2_ACT_LEAKY) v[i] = leaky(v[i]);
+        }
+        char* row = etl + (2 * (sp * 16 + pr) + b) * ERB;
+        if constexpr (is_x2<OutT>::value) {   // a group of 8 channels: 16 bytes of hi parts, 16 bytes of lo parts
+          typedef __attribute__((ext_vector_type(4))) _Float16 h4;
+          h4 h, l;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            h[i] = (_Float16)v[i];
+            l[i] = (_Float16)(v[i] - (float)h[i]);
+          }
+          char* grp = row + (g16 >> 1) * 32 + (g16 & 1) * 8;
+          *reinterpret_cast<h4*>(grp) = h;
+          *reinterpret_cast<h4*>(grp + 16) = l;
+        } else {
+          *reinterpret_cast<float4*>(row + g16 * 16) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+      }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the tile is read back by other lanes of the wave)
+    const int uy = toy * 2 + phase, ux0 = (tox + wave * 32) * 2;   // the wave's 64 output pixels: (tn, uy, ux0 + R)
+    char* const ob = reinterpret_cast<char*>(out + (((size_t)tn * p.out_H + uy) * p.out_W + ux0) * p.out_cs + p.out_c0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int R = i * 16 + (lane >> 2), part = lane & 3;
+      *reinterpret_cast<uint4*>(ob + (size_t)R * p.out_cs * sizeof(OutT) + part * 16) =
+          *reinterpret_cast<const uint4*>(etl + R * ERB + part * 16);
+    }
+    if (p.up_src != nullptr) halo_upflow_pixel<OutT>(p, out, tn, uy, ux0 + lane);
+    return;
+  }
 
   const int fr = lane & 31, fh = lane >> 5, fsw = (fr >> 1) & 7;
   f32x16 acc[TCN][TPN];
@@ -1063,13 +1246,15 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(const ConvArgs p) {
         bl[t] = lb[rb * 8 + ((4 * q + 2 * fh + 1) ^ sw)];
       }
 #pragma unroll
-      for (int tc = 0; tc < TCN; ++tc)
+      for (int tc = 0; tc < TCN; ++tc) {
+        if (kPT && kx != tc && kx != tc + 1) continue;  // tile tc = column phase tc: window columns tc and tc + 1
 #pragma unroll
         for (int tp = 0; tp < TPN; ++tp) {
           acc[tc][tp] = mfma_32x32x16<f16_t>(al[tc], bh[tp], acc[tc][tp]);
           acc[tc][tp] = mfma_32x32x16<f16_t>(ah[tc], bl[tp], acc[tc][tp]);
           acc[tc][tp] = mfma_32x32x16<f16_t>(ah[tc], bh[tp], acc[tc][tp]);
         }
+      }
     }
 #if FN2_SETPRIO
     __builtin_amdgcn_s_setprio(0);
@@ -1142,30 +1327,8 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(const ConvArgs p) {
         for (int q = 0; q < 16; ++q)
           if (cout_base + q < p.Cout) store_elem<OutT>(po + q, v[q]);
       }
-      if (p.merged && p.up_src != nullptr && cout_base == 0 && ox < p.OW) {
-        // upsample_flowXtoY of this output pixel (upsample_flow_kernel's arithmetic, tap for tap; conv.hip)
-        const int uy = toy * osc + oy_off, ux = ox * osc + ox_off + bsel;
-        const int H2 = p.out_H >> 1, W2 = p.out_W >> 1;
-        const int a = uy & 1, b = ux & 1, y = uy >> 1, x = ux >> 1;
-        float r0 = p.up_bias ? p.up_bias[0] : 0.f, r1 = p.up_bias ? p.up_bias[1] : 0.f;
-#pragma unroll
-        for (int ty = 0; ty < 2; ++ty) {
-          const int iy = y - 1 + a + ty, ky = 3 - a - 2 * ty;
-          if (iy < 0 || iy >= H2) continue;
-#pragma unroll
-          for (int tx = 0; tx < 2; ++tx) {
-            const int ix = x - 1 + b + tx, kx = 3 - b - 2 * tx;
-            if (ix < 0 || ix >= W2) continue;
-            const float2 sv = *reinterpret_cast<const float2*>(p.up_src + (((long)tn * H2 + iy) * W2 + ix) * 2);
-            const float* ww = p.up_w + (ky * 4 + kx) * 4;
-            r0 += sv.x * ww[0] + sv.y * ww[1];
-            r1 += sv.x * ww[2] + sv.y * ww[3];
-          }
-        }
-        OutT* pu = out + (((size_t)tn * p.out_H + uy) * p.out_W + ux) * p.out_cs + p.up_c0;
-        store_elem<OutT>(pu, r0);
-        store_elem<OutT>(pu + 1, r1);
-      }
+      if (p.merged && p.up_src != nullptr && cout_base == 0 && ox < p.OW)
+        halo_upflow_pixel<OutT>(p, out, tn, toy * osc + oy_off, ox * osc + ox_off + bsel);
     }
   }
 #endif  // __HIP_DEVICE_COMPILE__
@@ -1695,7 +1858,21 @@ static bool launch_halo(const ConvArgs& a, int tile, int phases, hipStream_t s) 
   const int bp = tile == 128 ? 64 : 128;
   if (a.OW % bp != 0 || a.M % bp != 0) return false;
   dim3 block(256);
-#define FN2_HALO(GY, ...)                                                                         \
+  // kind 5: each column phase walks its own two window columns (conv_halo_kernel, PT): the 32-row tile of 16 outputs as two
+  // 16-row tiles, the two 32-row tiles of 32 outputs in ONE block (the row is fetched once).  FN2_CONV_DBG bit 128 = the
+  // all-columns walk (A/B).  The 16-output form stores whole pixels: accumulating / masked launches and fp32 views off
+  // the 32-byte grid keep the all-columns walk.
+  if (a.merged && !(a.dbg & 128) && tile == 32 &&
+      (a.Cout == 32 || (!a.accum && a.mask_y == nullptr && a.out_cs % 8 == 0 && a.out_c0 % 8 == 0))) {
+    dim3 grid(a.M / bp, 1, phases);
+    if (conv_name_sink().buf)
+      snprintf(conv_name_sink().buf, conv_name_sink().cap, "conv_halo_kernel<%s, 1, 4, %d, 1, 3, 1>",
+               is_x2<OutT>::value ? "fn2::x2_t" : "float", a.Cout / 16);
+    else if (a.Cout == 32) hipLaunchKernelGGL((conv_halo_kernel<OutT, 1, 4, 2, 1, 3, 1>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((conv_halo_kernel<OutT, 1, 4, 1, 1, 3, 1>), grid, block, 0, s, a);
+    return true;
+  }
+#define FN2_HALO(GY, ...)                                                                        \
   do {                                                                                            \
     dim3 grid(a.M / bp, GY, phases);                                                              \
     if (conv_name_sink().buf)                                                                     \

@@ -385,8 +385,10 @@ class Engine:
         in_code = self._code(sbuf)
         esz = 2 if in_code in (_hip.FN2_BF16, _hip.FN2_F16) else 4
         # transposed convs with 16 outputs on wide maps (the fusion net's fuse_deconv0): both column phases of an output row
-        # in one block (fn2_conv2d kind 5): 164.6 -> 116.9 us.  With 32 outputs (fuse_deconv1) the four-phase form has no
-        # half-empty tile to begin with and the third tap slot only adds work: 39.8 -> 50.6 us, not taken.
+        # in one block (fn2_conv2d kind 5): 164.6 -> 116.9 us, and 137.6 -> 94.4 us with each column phase walking only the two
+        # window columns it has weights for.  With 32 outputs (fuse_deconv1) the four-phase form has no
+        # half-empty tile to begin with: the all-columns walk lost (39.8 -> 50.6 us) and the per-phase walk only ties
+        # (30.8 four-phase, 30.5 us merged), so it is not taken.
         # Inference engines only; FN2_DECONV_MERGED=0: off (A/B).  (16 outputs of a split-fp16 layer: the 32-row tile of the
         # LDS-DMA kernel, the only plan fn2_conv2d_plan has for them)
         merged = (kind != "conv" and self.compose_heads and cout == 16 and in_code == _hip.FN2_F16X2

@@ -35,6 +35,10 @@ LAYERS = {  # name: (kind, k, stride, pad, cin, cout, N, H, W) -- FlowNetC batch
     "fuse_interconv0": ("conv", 3, 1, 1, 82, 16, 4, 384, 512),
     "fuse_interconv1": ("conv", 3, 1, 1, 162, 32, 4, 192, 256),
     "fuse_deconv0": ("deconv", 4, 2, 1, 162, 16, 4, 192, 256),
+    "fuse_deconv1": ("deconv", 4, 2, 1, 128, 32, 4, 96, 128),
+    # ... as fn2_conv2d kind 5 (column phases merged; FN2_CONV_DBG bit 128 = every phase walks all three window columns)
+    "fuse_deconv0_m": ("deconvm", 4, 2, 1, 162, 16, 4, 192, 256),
+    "fuse_deconv1_m": ("deconvm", 4, 2, 1, 128, 32, 4, 96, 128),
     "fuse_conv1_1": ("conv", 3, 1, 1, 64, 128, 4, 192, 256),
     # the weight-streaming levels at FlowNet2's batch 4
     "conv5_b4": ("conv", 3, 2, 1, 512, 512, 4, 24, 32),
@@ -74,7 +78,7 @@ def build(name, dtype):
     cin_line = (cin + line - 1) // line * line
     cin_pad = cin_line if _hip.conv_plan(code, cin_line, cout).layout == 1 else (cin + 7) // 8 * 8
     plan = _hip.conv_plan(code, cin_pad, cout)
-    pack = W.pack_conv if kind == "conv" else W.pack_deconv
+    pack = W.pack_conv if kind == "conv" else W.pack_deconv_merged if kind == "deconvm" else W.pack_deconv
     packed, cin_pad, cout_pad, kpad = pack(w, plan.cout_tile, plan.kstep_elems, cin_pad, plan.layout)
     layout = plan.layout
     wdev = W.packed_to_device(packed, plan.wgt_dtype, "cuda")
@@ -82,7 +86,7 @@ def build(name, dtype):
     d = _hip.Fn2ConvDesc()
     d.inp, d.out = _hip.view(x, cin, 0, code), _hip.view(out, cout, 0, code)
     d.wgt, d.bias = wdev.data_ptr(), None
-    d.kind = 0 if kind == "conv" else 1
+    d.kind = 0 if kind == "conv" else 5 if kind == "deconvm" else 1
     d.kh = d.kw = k
     d.stride, d.pad, d.act = stride, pad, 1
     d.cin_pad, d.cout_pad, d.kpad, d.wgt_layout = cin_pad, cout_pad, kpad, layout
