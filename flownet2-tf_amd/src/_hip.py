@@ -47,6 +47,11 @@ class Fn2BwdwDesc(C.Structure):
                 ("cout_pad", C.c_int32), ("kpad", C.c_int32), ("wgt_layout", C.c_int32), ("db", C.c_void_p)]
 
 
+class Fn2HfemLevel(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("label", C.c_void_p), ("epe", C.c_void_p), ("weight", C.c_void_p),
+                ("npix", C.c_int64), ("k", C.c_int64), ("hard_weight", C.c_float)]
+
+
 _i, _p, _f = C.c_int, C.c_void_p, C.c_float
 _ip = C.POINTER(C.c_int)
 _tp = C.POINTER(Fn2Tensor)
@@ -102,6 +107,8 @@ PROTOTYPES = {
     "fn2_fusion_input_pf": (_i, [_p, _p, _p, _f, _p, _p, _f, _p, _i, _i, _tp, _i, _p]),
     "fn2_epe_loss_grad": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _p]),
     "fn2_epe_loss_grad_weighted": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _p]),
+    "fn2_hfem_hard_weights": (_i, [C.POINTER(Fn2HfemLevel), _i, _p]),
+    "fn2_hfem_edge_weights": (_i, [_p, _f, _p, C.c_int64, _p]),
     "fn2_leaky_bwd": (_i, [_tp, _tp, _p, _p]),
     "fn2_bias_grad": (_i, [_tp, _p, _p]),
     "fn2_gather_f32": (_i, [_p, _p, _p, C.c_int64, _p]),

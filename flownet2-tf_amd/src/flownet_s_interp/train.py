@@ -60,8 +60,7 @@ def main(flags):
                                   num_distrib=getattr(flags, "num_matches_distributions", 2),
                                   min_val=getattr(flags, "min_val_dense", 0), ff_like=getattr(flags, "ff_like", -1))
     for step, (img, matches, sparse, edges, flow) in enumerate(batches, step0 + 1):
-        loss = tr.forward_backward_interp(img, matches, sparse, flow, edges=edges, reduce=True)
-        tr.apply_gradients(reduced_world=tr.wait_reduction())
+        loss = tr.train_step_interp(img, matches, sparse, flow, edges=edges)  # (the captured step, every loss mode)
         if rank == 0 and (step % flags.log_every == 0 or step == end):
             print("global step %6d | loss %.5f | %.1f samples/s" % (step, float(loss.item()), world * flags.batch *
                                                                     (step - step0) / (time.perf_counter() - t0)), flush=True)

@@ -1,8 +1,9 @@
 """Training losses of the reference (FlowNetS.loss, src/flownet_s/flownet_s.py:122-161;
 average_endpoint_error, src/utils.py:209-224; FlowNet2.loss, src/flownet2/flownet2.py:107-116).
 The NaN-aware ground-truth downsample (with the label scaling inside it) and the endpoint-error reductions are
-calls into libflownet2_hip.so (fn2_downsample_scaled_f32, fn2_epe_loss_grad); only the top-k selection of the
-'hard' mining mode of FlowNetS_interp's loss is a torch device op."""
+calls into libflownet2_hip.so (fn2_downsample_scaled_f32, fn2_epe_loss_grad), and so are the pixel weights of the
+mining modes of FlowNetS_interp's loss that the trainer uses (hard_example_weights: fn2_hfem_hard_weights); only the
+scalar average_endpoint_error_hfem below still selects with torch.topk."""
 import numpy as np
 import torch
 
@@ -58,6 +59,50 @@ def average_endpoint_error_hfem(labels, predictions, add_hfem='', lambda_w=2., p
     if mode == 'edges' and edges is not None:
         return (epe + lambda_w * epe * _as_dev(edges, epe).float()).sum() / n
     return epe.sum() / n
+
+
+def hard_k(numel, perc_hfem):
+    """Number of hard pixels among `numel`: round(perc_hfem / 100 * numel) in fp32 with tf.round's half-to-even
+    (utils.py:268-275)."""
+    return int(np.round(np.float32(perc_hfem / 100) * np.float32(numel)))
+
+
+def hfem_level(pred, label, epe, weight, k, hard_weight):
+    """One fn2_hfem_level over contiguous fp32 device tensors (pred, label [..., 2]; epe, weight one value per pixel)."""
+    return _hip.Fn2HfemLevel(pred.data_ptr(), label.data_ptr(), epe.data_ptr(), weight.data_ptr(), epe.numel(), int(k),
+                             float(hard_weight))
+
+
+def hard_weight_of(numel, k, lambda_w):
+    """(1 + lambda) * #pixels / #hard pixels as fp32 (utils.py:305-312); 0 when no pixel is hard."""
+    return np.float32((1.0 + lambda_w) * (numel / k)) if k > 0 else np.float32(0.0)
+
+
+def hard_example_weights(labels, predictions, perc_hfem=50, lambda_w=2.0, return_epe=False):
+    """The pixel weights of the 'hard' mining mode for one [N,H,W,2] pair of device tensors: (1 + lambda_w) * N H W / k
+    on the k = hard_k(N H W, perc_hfem) pixels of the batch with the largest endpoint error, 0 elsewhere.  Equal values
+    are taken in index order, as tf.nn.top_k takes them (utils.py:282).  One fn2_hfem_hard_weights launch, no sort.
+    Returns the [N,H,W] fp32 weight map, and with return_epe the [N,H,W] endpoint-error map as well."""
+    if not 0 <= perc_hfem <= 100:
+        raise ValueError("hard_example_weights: perc_hfem must lie in [0, 100], not %r" % (perc_hfem,))
+    if not (isinstance(labels, torch.Tensor) and isinstance(predictions, torch.Tensor)):
+        raise ValueError("hard_example_weights: labels and predictions must be device tensors")
+    if labels.shape != predictions.shape or predictions.ndim != 4 or predictions.shape[3] != 2:
+        raise ValueError("hard_example_weights: labels and predictions must both be [N, H, W, 2]")
+    if not (labels.is_cuda and predictions.is_cuda):
+        raise ValueError("hard_example_weights: labels and predictions must be device tensors, not CPU tensors")
+    pred = predictions.detach().to(dtype=torch.float32).contiguous()
+    lab = labels.detach().to(device=pred.device, dtype=torch.float32).contiguous()
+    n, h, w, _ = pred.shape
+    numel = n * h * w
+    if numel < 1:
+        raise ValueError("hard_example_weights: empty tensors")
+    k = hard_k(numel, perc_hfem)
+    epe = torch.empty((n, h, w), dtype=torch.float32, device=pred.device)
+    weight = torch.empty_like(epe)
+    level = hfem_level(pred, lab, epe, weight, k, hard_weight_of(numel, k, lambda_w))
+    _hip.check(_hip.lib().fn2_hfem_hard_weights(level, 1, _hip.stream_ptr()))
+    return (weight, epe) if return_epe else weight
 
 
 def mean_endpoint_error(gt_flow, pred_flow):

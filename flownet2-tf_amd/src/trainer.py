@@ -636,33 +636,44 @@ class FlowNetSTrainer:
         from .training_schedules import learning_rate
         return learning_rate(self.schedule, step, getattr(self, "train_params", None))
 
-    def forward_backward_interp(self, input_a, matches_a, sparse_flow, gt_flow, edges=None, reduce=False):
+    def _pack_interp(self, input_a, matches_a, sparse_flow):
         """FlowNetS_interp: the tower's second 'image' is [0.05 * sparse_flow | matches] (flownet_s_interp.py:34-38)."""
         dev = lambda x: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(
             device=self.dev, dtype=torch.float32)
         m = dev(matches_a)
         if m.ndim == 3:
             m = m[..., None]
-        return self.forward_backward(dev(input_a), torch.cat([dev(sparse_flow) * 0.05, m], dim=3), gt_flow, reduce=reduce,
-                                     edges=edges)
+        return dev(input_a), torch.cat([dev(sparse_flow) * 0.05, m], dim=3)
+
+    def forward_backward_interp(self, input_a, matches_a, sparse_flow, gt_flow, edges=None, reduce=False):
+        """forward_backward on the packed inputs of FlowNetS_interp (_pack_interp)."""
+        a, b = self._pack_interp(input_a, matches_a, sparse_flow)
+        return self.forward_backward(a, b, gt_flow, reduce=reduce, edges=edges)
+
+    def train_step_interp(self, input_a, matches_a, sparse_flow, gt_flow, edges=None):
+        """train_step on the packed inputs of FlowNetS_interp; the packing happens outside the captured graph."""
+        a, b = self._pack_interp(input_a, matches_a, sparse_flow)
+        return self.train_step(a, b, gt_flow, edges=edges)
 
     def _pixel_weights(self, pred, label, edges_dev):
-        """Per-pixel loss weights of the mining modes (None for plain AEPE).  The selection itself (top-k over the
-        batch's EPE map, a few thousand to a few hundred thousand values) is a torch device op; the weighted loss and
-        its gradient stay in the HIP kernel."""
+        """Per-pixel loss weights of the mining modes on the eager path (None for plain AEPE), one level per call: the
+        exact top-k selection of 'hard' (fn2_hfem_hard_weights) or 1 + lambda * downsampled edges."""
         if self.hfem == "hard":
-            d = pred - label
-            epe = torch.sqrt((d * d).sum(dim=3)).reshape(-1)
-            k = int(np.round(np.float32(self.hard_perc / 100) * np.float32(epe.numel())))  # tf.round: half to even
-            wgt = torch.zeros_like(epe)
-            if k > 0:
-                wgt[torch.topk(epe, k).indices] = (1.0 + self.lambda_w) * (epe.numel() / k)
-            return wgt
+            from .losses import hard_example_weights
+            return hard_example_weights(label, pred, self.hard_perc, self.lambda_w).reshape(-1)
         if self.hfem == "edges" and edges_dev is not None:
             from .downsample import downsample
             e = downsample(edges_dev, [pred.shape[1], pred.shape[2]])
-            return (1.0 + self.lambda_w * e[..., 0]).contiguous().reshape(-1)
+            wgt = torch.empty(e.numel(), dtype=torch.float32, device=e.device)
+            _hip.check(self.lib.fn2_hfem_edge_weights(_hip.ptr(e), self.lambda_w, _hip.ptr(wgt), e.numel(), _hip.stream_ptr()))
+            return wgt
         return None
+
+    def _edges_dev(self, edges):
+        """An edge map given as [N,H,W] or [N,H,W,1], as a fp32 [N,H,W,1] device tensor."""
+        e = (edges if isinstance(edges, torch.Tensor) else torch.as_tensor(np.asarray(edges))).to(
+            device=self.dev, dtype=torch.float32)
+        return e[..., None] if e.ndim == 3 else e
 
     def forward_backward(self, input_a, input_b, gt_flow, reduce=False, edges=None):
         """Loss and all parameter gradients (left in self.grad_arena).  Returns the loss as a device scalar.
@@ -674,12 +685,7 @@ class FlowNetSTrainer:
         self._zero_buffers(s)
         eng.launch()
         # ---- loss and its gradient at the five scales (flownet_s.py:122-158)
-        edges_dev = None
-        if edges is not None:
-            edges_dev = (edges if isinstance(edges, torch.Tensor) else torch.as_tensor(np.asarray(edges))).to(
-                device=self.dev, dtype=torch.float32)
-            if edges_dev.ndim == 3:
-                edges_dev = edges_dev[..., None]
+        edges_dev = None if edges is None else self._edges_dev(edges)
         for pname, wgt in self.loss_terms.items():
             pred = eng.outputs[pname]
             n, h, w, _ = pred.shape
@@ -897,17 +903,22 @@ class FlowNetSTrainer:
             self.step_count = int(np.asarray(state["global_step"]).reshape(-1)[0])
         return n
 
-    def train_step(self, input_a, input_b, gt_flow):
+    def train_step(self, input_a, input_b, gt_flow, edges=None):
         """One step: forward, loss, backward, gradient all-reduce (data parallel), Adam.  The launch sequence is
         captured once as hipGraph segments (cut where a gradient bucket is handed to the all-reduce) and replayed:
-        the per-step scalars of Adam live in device memory, so nothing in the segments changes between steps.
-        FN2_TRAIN_GRAPH=0, or the mining losses (their top-k selection allocates): the eager launch sequence."""
+        the per-step scalars of Adam live in device memory, so nothing in the segments changes between steps.  The
+        mining losses are part of the graph: their pixel weights come from fn2_hfem_hard_weights (one launch for the
+        five scales) or fn2_hfem_edge_weights, on buffers allocated before the capture.
+        edges: the edge map of the 'edges' mode, [N,H,W] or [N,H,W,1]; the other modes ignore it.  Whether it is given
+        is fixed by the first captured step ('edges' without a map is plain AEPE, as on the eager path): a later step
+        that contradicts that choice raises ValueError.
+        FN2_TRAIN_GRAPH=0: the eager launch sequence."""
         import os
-        if self.hfem or not int(os.environ.get("FN2_TRAIN_GRAPH", "1")):
-            loss = self.forward_backward(input_a, input_b, gt_flow, reduce=True)
+        if not int(os.environ.get("FN2_TRAIN_GRAPH", "1")):
+            loss = self.forward_backward(input_a, input_b, gt_flow, reduce=True, edges=edges)
             self.apply_gradients(reduced_world=self.wait_reduction())
             return loss
-        return self._train_step_graph(input_a, input_b, gt_flow)
+        return self._train_step_graph(input_a, input_b, gt_flow, edges)
 
     # ------------------------------------------------------------------ captured step
     def _segment_body(self, seg):
@@ -927,8 +938,11 @@ class FlowNetSTrainer:
                 label = self._labels[pname]
                 _hip.check(self.lib.fn2_downsample_scaled_f32(_hip.ptr(self.gt), self.gt_scale, _hip.ptr(label), n, self.H,
                                                               self.W, 2, h, w, s))
-                _hip.check(self.lib.fn2_epe_loss_grad(_hip.ptr(pred), _hip.ptr(label), _hip.ptr(self._gbuf(pred)),
-                                                      _hip.ptr(self.loss_dev), n, h, w, wgt, self.loss_scale, s))
+                if self._mining is None:
+                    _hip.check(self.lib.fn2_epe_loss_grad(_hip.ptr(pred), _hip.ptr(label), _hip.ptr(self._gbuf(pred)),
+                                                          _hip.ptr(self.loss_dev), n, h, w, wgt, self.loss_scale, s))
+            if self._mining is not None:
+                self._mining_body(s)
         if seg < nseg:
             lo = 0 if seg == 0 else self._seg_ends[seg - 1] + 1
             # (the filter gradients as a parallel path of the graph -- they need only the layer's finished output
@@ -947,6 +961,47 @@ class FlowNetSTrainer:
                                                     _hip.ptr(self._adam_l2), len(self.params), _hip.ptr(self._hyper), s))
         self.refresh_backward_weights(forward=False)
 
+    def _alloc_mining(self, with_edges):
+        """Everything the mining losses of the captured step write, allocated before the capture: per loss scale the
+        endpoint-error and weight maps and, for 'edges', the downsampled edge map, plus the static input self.edges_in.
+        self._mining: None (plain AEPE: also 'edges' without an edge map), 'hard' or 'edges'."""
+        from .losses import hard_k, hard_weight_of, hfem_level
+        self._mining = self.hfem if self.hfem == "hard" or (self.hfem == "edges" and with_edges) else None
+        if self._mining is None:
+            return
+        new = lambda shape: torch.zeros(shape, dtype=torch.float32, device=self.dev)
+        self._hfem_weight = {p: new(self.eng.outputs[p].shape[:3]) for p in self.loss_terms}
+        if self._mining == "edges":
+            self.edges_in = new((self.N, self.H, self.W, 1))
+            self._edge_maps = {p: new(tuple(self.eng.outputs[p].shape[:3]) + (1,)) for p in self.loss_terms}
+            return
+        self._hfem_epe = {p: new(self.eng.outputs[p].shape[:3]) for p in self.loss_terms}
+        levels = []
+        for p in self.loss_terms:
+            numel = self._hfem_epe[p].numel()
+            k = hard_k(numel, self.hard_perc)
+            levels.append(hfem_level(self.eng.outputs[p], self._labels[p], self._hfem_epe[p], self._hfem_weight[p], k,
+                                     hard_weight_of(numel, k, self.lambda_w)))
+        self._hfem_levels = (_hip.Fn2HfemLevel * len(levels))(*levels)
+
+    def _mining_body(self, s):
+        """Segment 0 behind the labels: the pixel weights of every scale ('hard': one launch for all of them), then the
+        weighted loss and its gradient per scale."""
+        lib = self.lib
+        if self._mining == "hard":
+            _hip.check(lib.fn2_hfem_hard_weights(self._hfem_levels, len(self._hfem_levels), s))
+        for pname, wgt in self.loss_terms.items():
+            pred = self.eng.outputs[pname]
+            n, h, w, _ = pred.shape
+            pw = self._hfem_weight[pname]
+            if self._mining == "edges":
+                e = self._edge_maps[pname]
+                _hip.check(lib.fn2_downsample_f32(_hip.ptr(self.edges_in), _hip.ptr(e), n, self.H, self.W, 1, h, w, s))
+                _hip.check(lib.fn2_hfem_edge_weights(_hip.ptr(e), self.lambda_w, _hip.ptr(pw), pw.numel(), s))
+            _hip.check(lib.fn2_epe_loss_grad_weighted(_hip.ptr(pred), _hip.ptr(self._labels[pname]), _hip.ptr(pw),
+                                                      _hip.ptr(self._gbuf(pred)), _hip.ptr(self.loss_dev), n, h, w, wgt,
+                                                      self.loss_scale, s))
+
     def _build_adam_tables(self):
         """{w, m, v, g, split-fp16 forward copy of w (or 0), its scale} per parameter tensor (fn2_adam_step_multi): Adam
         rewrites the copy the forward convolutions read while it has the new master in registers."""
@@ -962,13 +1017,14 @@ class FlowNetSTrainer:
         self._adam_counts = torch.tensor([p["n"] for p in self.params], dtype=torch.int64, device=self.dev)
         self._adam_l2 = torch.tensor([l2 if p["reg"] else 0.0 for p in self.params], dtype=torch.float32, device=self.dev)
 
-    def _capture_step(self):
+    def _capture_step(self, with_edges=False):
         from .dist import exchange_enabled
         # one segment per gradient bucket when the gradients are exchanged, else a single backward segment
         self._seg_ends = [i for i, _ in self.buckets] if exchange_enabled() else [len(self.bwd_ops) - 1]
         self._labels = {pname: torch.empty_like(self.eng.outputs[pname]) for pname in self.loss_terms}
         for pname in self.loss_terms:
             self._gbuf(self.eng.outputs[pname])  # allocate outside the capture
+        self._alloc_mining(with_edges)
         self._hyper = torch.zeros(5, dtype=torch.float32, device=self.dev)
         self._hyper_host = torch.zeros(5, dtype=torch.float32).pin_memory()
         self._build_adam_tables()
@@ -993,10 +1049,16 @@ class FlowNetSTrainer:
         torch.cuda.current_stream().wait_stream(side)
         self._step_graphs = graphs
 
-    def _train_step_graph(self, input_a, input_b, gt_flow):
+    def _train_step_graph(self, input_a, input_b, gt_flow, edges=None):
         from .dist import allreduce_bucket_async, exchange_enabled, world_size
+        with_edges = self.hfem == "edges" and edges is not None
         if getattr(self, "_step_graphs", None) is None:
-            self._capture_step()
+            self._capture_step(with_edges)
+        if with_edges != (self._mining == "edges"):
+            raise ValueError("train_step: the captured step was built %s an edge map; this call is %s one"
+                             % (("without", "with") if with_edges else ("with", "without")))
+        if with_edges:
+            self.edges_in.copy_(self._edges_dev(edges).reshape(self.edges_in.shape), non_blocking=True)
         self.gt.copy_(torch.as_tensor(gt_flow).to(dtype=torch.float32), non_blocking=True)
         self.eng.set_inputs(input_a, input_b)
         world = world_size()

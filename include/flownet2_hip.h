@@ -392,6 +392,26 @@ int fn2_epe_loss_grad(const float* pred, const float* label, float* dpred, float
  * EPE pixels of the batch and 0 elsewhere; 'edges': 1 + lambda * edges.  L = weight / n * sum w_pix ||pred - label||. */
 int fn2_epe_loss_grad_weighted(const float* pred, const float* label, const float* pixel_weight, float* dpred,
                                float* loss_accum, int n, int h, int w, float weight, float grad_mult, void* stream);
+/* The pixel weights of the two mining modes, for fn2_epe_loss_grad_weighted; no allocation, no host synchronisation.
+ *
+ * 'hard': one entry per loss scale.  epe[i] = ||pred[i] - label[i]||_2; weight[i] = hard_weight for the k pixels that
+ * come first under "larger epe first, then lower flat index first" (a stable descending sort: tf.nn.top_k,
+ * utils.py:282) and 0 for the others.  A NaN epe counts as the largest value.  k = 0 writes zeros, k = npix writes
+ * hard_weight everywhere.  `levels` is a HOST array of 1..8 entries (npix 1..2^31-1, 0 <= k <= npix, no null pointer);
+ * it travels to the kernel by value, so a captured graph keeps the table it was captured with.  All levels run in
+ * ONE launch, one workgroup per level; epe doubles as the workspace of the selection. */
+typedef struct {
+  const float* pred;  /* [npix, 2] fp32, contiguous */
+  const float* label; /* [npix, 2] */
+  float* epe;         /* [npix] out */
+  float* weight;      /* [npix] out */
+  int64_t npix;
+  int64_t k;
+  float hard_weight;
+} fn2_hfem_level;
+int fn2_hfem_hard_weights(const fn2_hfem_level* levels, int n_levels, void* stream);
+/* 'edges': weight[i] = 1 + lambda_w * edges[i], product and sum rounded separately. */
+int fn2_hfem_edge_weights(const float* edges, float lambda_w, float* weight, int64_t npix, void* stream);
 /* g *= LeakyReLU'(.) evaluated from the layer output y (utils.py:401-405: 1 for y > 0, 0.1 for y < 0, 0.55 at +-0); y, g
  * channel-slice views, both fp32 (c, cs, c0 multiples of 4) or both split fp16 (multiples of 8); y is only read.
  * db != NULL: the bias gradient of the same layer in the same pass, ADDED: db[c] += sum over pixels of the new g. */
