@@ -11,7 +11,7 @@
 // One pixel per lane, a wave along x: a wave owns 64 consecutive pixels of one row, so its own flows are one coalesced
 // 512-byte run and, for a smooth flow, the taps of neighbouring lanes are neighbours too (served from L2).  Waves walk
 // the (image, row, 64-pixel segment) units with a grid-stride loop: the block count is bounded for any size.
-#include "fn2_common.h"
+#include "tf_warp.h"
 
 namespace fn2 {
 namespace {
@@ -19,42 +19,6 @@ namespace {
 constexpr int OCC_BLOCK = 256;                  // four waves, each on its own unit
 constexpr int OCC_WAVES = OCC_BLOCK / 64;
 constexpr int OCC_MAX_BLOCKS = 4096;
-
-// tf.cast(float -> int32) made safe for every input: NaN -> 0, anything else saturates.  The bounds -2 and size + 1
-// already lie outside what the clamp below can tell apart, and truncation commutes with a clamp to integer bounds, so
-// every coordinate the reference defines gets the reference's index.
-__device__ __forceinline__ int trunc_sat(float v, int size) {
-  if (!(v == v)) return 0;
-  return (int)fminf(fmaxf(v, -2.0f), (float)size + 1.0f);
-}
-
-struct TfTaps {
-  int x0, x1, y0, y1;
-  float wa, wb, wc, wd;
-};
-
-__device__ __forceinline__ TfTaps tf_taps(int px, int py, float u, float v, int W, int H) {
-  TfTaps t;
-  const float x = (float)px + u, y = (float)py + v;  // :467, :473-474
-  const int tx = trunc_sat(x, W), ty = trunc_sat(y, H);  // :477-480
-  t.x0 = min(max(tx, 0), W - 1);                      // :483-486
-  t.x1 = min(max(tx + 1, 0), W - 1);
-  t.y0 = min(max(ty, 0), H - 1);
-  t.y1 = min(max(ty + 1, 0), H - 1);
-  const float x0f = (float)t.x0, x1f = (float)t.x1, y0f = (float)t.y0, y1f = (float)t.y1;  // :495-498
-  t.wa = (x1f - x) * (y1f - y);                       // :502-505
-  t.wb = (x1f - x) * (y - y0f);
-  t.wc = (x - x0f) * (y1f - y);
-  t.wd = (x - x0f) * (y - y0f);
-  return t;
-}
-
-// tf.add_n([wa*Ia, wb*Ib, wc*Ic, wd*Id]) (:514), left to right
-__device__ __forceinline__ float tf_blend(const TfTaps& t, float a, float b, float c, float d) {
-  return ((t.wa * a + t.wb * b) + t.wc * c) + t.wd * d;
-}
-
-__device__ __forceinline__ float2 ld2(const float* p) { return *reinterpret_cast<const float2*>(p); }
 
 // tf_warp of a two-channel map `src` (one image: row pitch in floats) at pixel (px, py) displaced by (u, v)
 __device__ __forceinline__ float2 tf_warp_c2(const float* __restrict__ src, int64_t pitch, int px, int py, float u,
@@ -64,20 +28,6 @@ __device__ __forceinline__ float2 tf_warp_c2(const float* __restrict__ src, int6
   const float* r1 = src + (int64_t)t.y1 * pitch;
   const float2 a = ld2(r0 + 2 * t.x0), b = ld2(r1 + 2 * t.x0), c = ld2(r0 + 2 * t.x1), d = ld2(r1 + 2 * t.x1);
   return make_float2(tf_blend(t, a.x, b.x, c.x, d.x), tf_blend(t, a.y, b.y, c.y, d.y));
-}
-
-// (image, row, first column) of the unit a wave works on
-struct Unit {
-  int64_t n;
-  int y, x;
-};
-__device__ __forceinline__ Unit unit_at(int64_t u, int H, int segs) {
-  Unit r;
-  const int64_t row = u / segs;
-  r.x = (int)(u - row * segs) * 64 + (int)(threadIdx.x & 63);
-  r.n = row / H;
-  r.y = (int)(row - r.n * H);
-  return r;
 }
 
 __global__ void __launch_bounds__(OCC_BLOCK) tf_warp_kernel(const float* __restrict__ img, int64_t img_pitch,

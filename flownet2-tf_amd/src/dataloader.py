@@ -57,21 +57,26 @@ def config_to_arrays(dataset_config):
     return out
 
 
-def read_list(path):
+def read_list(path, allow_unlabeled=False):
+    """Rows of a list file: `image_a image_b flow.flo`; with allow_unlabeled also `image_a image_b` (unsupervised
+    training needs no ground truth)."""
     with open(path) as f:
         rows = [ln.split() for ln in f.read().splitlines() if ln.strip()]
     for r in rows:
-        if len(r) != 3:
-            raise ValueError("expected `image_a image_b flow.flo` per line, got: %r" % (r,))
+        if len(r) != 3 and not (allow_unlabeled and len(r) == 2):
+            raise ValueError("expected `image_a image_b flow.flo`%s per line, got: %r"
+                             % (" or `image_a image_b`" if allow_unlabeled else "", r))
     return rows
 
 
-def _list_epoch(rows, rng):
-    """One epoch of (image_a, image_b, flow) host arrays from a list file, in a fresh random order."""
+def _list_epoch(rows, rng, with_flow=True):
+    """One epoch of (image_a, image_b, flow) host arrays from a list file, in a fresh random order; with_flow=False
+    leaves the ground truth unread (flow is None)."""
     from .net import imread
     for j in rng.permutation(len(rows)):
         r = rows[j]
-        yield imread(r[0]).astype(np.float32) / 255.0, imread(r[1]).astype(np.float32) / 255.0, read_flow(r[2])
+        yield (imread(r[0]).astype(np.float32) / 255.0, imread(r[1]).astype(np.float32) / 255.0,
+               read_flow(r[2]) if with_flow else None)
 
 
 def _tfrecord_epoch(path, rng, image_size, scale, shuffle_buffer):
@@ -98,23 +103,29 @@ def is_tfrecord(path):
 
 def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, data_augmentation=True, seed=0,
                  global_step=0, epochs=None, image_size=(384, 512), shuffle_buffer=256, augmentation="plugin",
-                 fast_mode=False):
+                 fast_mode=False, allow_unlabeled=False):
     """Generator of (image_a, image_b, flow) device tensors [B,h,w,3|3|2]; images in [0,1].  ``list_path`` is a
     text file of `image_a image_b flow.flo` triples or a ``.tfrecords`` file as the reference's converter writes it
     (``image_size`` = the dataset's PADDED_IMAGE_HEIGHT/WIDTH, dataset_configs.py:42-43).  With data_augmentation
     the crop is (crop_height, crop_width) and the flow is transformed with the two augmentation matrices
     (dataloader.py:480-540); without it the samples pass through unchanged.  ``augmentation='selflow'`` takes the
     augmentation the reference's live loader applies to image pairs instead of the plugin's (augment_all_estimation,
-    dataloader.py:93-113 -> src/data_augmentation.py): flips, a channel permutation and a colour chain per image, no crop."""
+    dataloader.py:93-113 -> src/data_augmentation.py): flips, a channel permutation and a colour chain per image, no crop.
+    ``allow_unlabeled`` (unsupervised training): a list file may hold `image_a image_b` lines, a third field is not read,
+    and the batches are (image_a, image_b, None); both augmentations transform a ground truth, so it needs
+    data_augmentation=False."""
     if augmentation not in ("plugin", "selflow"):
         raise ValueError("augmentation must be 'plugin' or 'selflow', got %r" % (augmentation,))
+    if allow_unlabeled and data_augmentation:
+        raise ValueError("allow_unlabeled needs data_augmentation=False: the augmentations transform a ground truth")
     rng = np.random.default_rng(seed)
-    rows = None if is_tfrecord(list_path) else read_list(list_path)
+    unlabeled = bool(allow_unlabeled) and not is_tfrecord(list_path)
+    rows = None if is_tfrecord(list_path) else read_list(list_path, allow_unlabeled)
     a_cfg, b_cfg = config_to_arrays(preprocess["image_a"]), config_to_arrays(preprocess["image_b"])
     crop = (preprocess["crop_height"], preprocess["crop_width"])
     epoch, step = 0, int(global_step)
     while epochs is None or epoch < epochs:
-        source = _list_epoch(rows, rng) if rows is not None else _tfrecord_epoch(
+        source = _list_epoch(rows, rng, not unlabeled) if rows is not None else _tfrecord_epoch(
             list_path, rng, image_size, bool(preprocess.get("scale", False)), shuffle_buffer)
         pick = []
         produced = False
@@ -122,11 +133,12 @@ def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, dat
             pick.append(smp)
             if len(pick) < batch_size:
                 continue
-            a, b, f = (np.stack([p[i] for p in pick]).astype(np.float32) for i in range(3))
+            a, b, f = (None if unlabeled and i == 2 else np.stack([p[i] for p in pick]).astype(np.float32)
+                       for i in range(3))
             pick = []
             produced = True
             if not data_augmentation:
-                dev = lambda x: torch.from_numpy(x).to(P._hip.require_device())
+                dev = lambda x: None if x is None else torch.from_numpy(x).to(P._hip.require_device())
                 yield dev(a), dev(b), dev(f)
             elif augmentation == "selflow":
                 from . import data_augmentation as DA

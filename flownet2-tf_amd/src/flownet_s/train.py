@@ -1,11 +1,14 @@
 """python -m src.flownet_s.train --list train.txt --out ./logs [--steps N --batch 8 --checkpoint w.npz --dtype f16x2
                                  --ckpt-format npz|tf --training_schedule one_cycle --optimizer sgd|momentum|adamw
-                                 --momentum M | --min_momentum A --max_momentum B --weight_decay D --clip_grad_norm C]
+                                 --momentum M | --min_momentum A --max_momentum B --weight_decay D --clip_grad_norm C
+                                 --unsupervised --no-augment --photometric_q Q --occ_alpha A --occ_beta B]
 The reference's src/flownet_s/train.py:8-40 + Net.train (net.py:1002-1400) over the HIP trainer: FlyingChairs-style
 augmentation on the GPU, multiscale EPE loss, Adam on LONG_SCHEDULE (or the optimiser and schedule named), periodic
 .npz checkpoints under the reference's variable names.  Data: a list file of `image_a image_b flow.flo` triples (the
 reference's TFRecords are built from exactly these).  Under torch.distributed.run every rank trains on its own shuffling of the list (seed + rank) and
-the gradients are all-reduced (data parallel)."""
+the gradients are all-reduced (data parallel).
+--unsupervised: no ground truth is read (`image_a image_b` lines are accepted); every pair runs in both directions, so
+--batch is even and batch / 2 pairs go in per step; the loss is the occlusion-aware photometric loss (src/photometric.py)."""
 import argparse
 import os
 import sys
@@ -112,7 +115,31 @@ def schedule_of(flags):
     return SCHEDULES[sched_name], {k: getattr(flags, k) for k, _ in POLICY_ARGUMENTS if getattr(flags, k, None) is not None}
 
 
+def add_unsupervised_arguments(ap):
+    ap.add_argument("--unsupervised", action="store_true",
+                    help="train without ground truth on the occlusion-aware photometric loss: `image_a image_b` lines are "
+                         "accepted, --batch is even (batch / 2 pairs per step, both directions); needs --no-augment")
+    ap.add_argument("--photometric_q", type=float, default=0.4, help="exponent of the robust loss (|d| + 0.01)^q")
+    ap.add_argument("--occ_alpha", type=float, default=0.01, help="forward-backward test: factor on the squared magnitudes")
+    ap.add_argument("--occ_beta", type=float, default=0.5, help="forward-backward test: constant, in pixels^2 of the level")
+
+
+def unsupervised_kwargs(flags):
+    """The trainer's unsupervised arguments from parsed flags, checked before anything touches a device."""
+    if not getattr(flags, "unsupervised", False):
+        return {}
+    if getattr(flags, "augment", True):
+        raise ValueError("--unsupervised needs --no-augment: both augmentations recolour the two frames independently, "
+                         "which breaks the brightness constancy the photometric loss assumes")
+    if flags.batch % 2:
+        raise ValueError("--unsupervised runs every pair in both directions: --batch must be even, got %d" % flags.batch)
+    from ..photometric import check_constants
+    alpha, beta, q = check_constants(flags.occ_alpha, flags.occ_beta, flags.photometric_q)
+    return dict(unsupervised=True, photometric_q=q, occ_alpha=alpha, occ_beta=beta)
+
+
 def main(flags):
+    unsup = unsupervised_kwargs(flags)
     import torch
     from .. import weights as W
     from ..trainer import FlowNetSTrainer
@@ -130,7 +157,7 @@ def main(flags):
             else (flags.height, flags.width))
     schedule, train_params = schedule_of(flags)
     tr = FlowNetSTrainer(wts, flags.batch, h, w, schedule=schedule, dtype=flags.dtype, model=model,
-                         **optimizer_kwargs(flags))
+                         **optimizer_kwargs(flags), **unsup)
     tr.train_params = train_params
     if flags.checkpoint:  # Adam moments + global_step, when the checkpoint carries them (ours and the reference's do)
         state = load_full_checkpoint(flags.checkpoint)
@@ -141,14 +168,16 @@ def main(flags):
     t0 = time.perf_counter()
     step0 = tr.step_count
     end = step0 + flags.steps  # --steps counts the steps of THIS run; `step` is the global step (schedule, file names)
-    for step, (a, b, f) in enumerate(load_batches(flags.list, flags.batch, pre, flags.augment, seed=flags.seed + rank,
-                                                  global_step=step0, augmentation=augmentation), step0 + 1):
-        loss = tr.train_step(a, b, f)
+    pairs = flags.batch // 2 if unsup else flags.batch  # (an unsupervised step fills two slots per pair)
+    for step, (a, b, f) in enumerate(load_batches(flags.list, pairs, pre, flags.augment, seed=flags.seed + rank,
+                                                  global_step=step0, augmentation=augmentation,
+                                                  allow_unlabeled=bool(unsup)), step0 + 1):
+        loss = tr.train_step_unsupervised(a, b) if unsup else tr.train_step(a, b, f)
         if step % flags.log_every == 0 or step == end:
             val = float(loss.item()) + (tr.l2_term() if flags.report_l2 else 0.0)
             if rank == 0:
                 # rate of THIS run: steps since the resumed global step, not the global step
-                print("global step %6d | loss %.5f | %.1f pairs/s" % (step, val, world * flags.batch * (step - step0) /
+                print("global step %6d | loss %.5f | %.1f pairs/s" % (step, val, world * pairs * (step - step0) /
                                                                       (time.perf_counter() - t0)), flush=True)
         val_every = getattr(flags, "val_every", 0)
         validate = bool(getattr(flags, "val_list", None) and val_every and (step % val_every == 0 or step == end))
@@ -199,6 +228,7 @@ def build_parser():
     ap.add_argument("--val-batches", dest="val_batches", type=int, default=None, help="at most this many validation batches")
     add_schedule_arguments(ap)
     add_optimizer_arguments(ap)
+    add_unsupervised_arguments(ap)
     return ap
 
 

@@ -65,7 +65,8 @@ def _index_hwio_uncached(rec):
 class FlowNetSTrainer:
     def __init__(self, weights, batch, height, width, schedule=LONG_SCHEDULE, eps=1e-8, dtype="f32", model="FlowNetS",
                  add_hard_flow_mining="", lambda_weight=2.0, hard_examples_perc=50, optimizer="adam", momentum=None,
-                 min_momentum=0.85, max_momentum=0.95, weight_decay=None, clip_grad_norm=-1.0):
+                 min_momentum=0.85, max_momentum=0.95, weight_decay=None, clip_grad_norm=-1.0, unsupervised=False,
+                 photometric_q=0.4, occ_alpha=0.01, occ_beta=0.5):
         """dtype 'f32': everything on the fp32 matrix cores.  'f16x2': activations, activation gradients and the
         weight copies the convolutions read are split fp16 (3 fp16 MFMAs per product, fp32 accumulate); the master
         weights, their gradients and the Adam state stay fp32.
@@ -74,7 +75,12 @@ class FlowNetSTrainer:
         cyclical between min_momentum and max_momentum along a computed rate policy) or 'adamw' (decoupled
         `weight_decay`, default 1e-4).  For 'momentum' a given weight_decay replaces the schedule's l2_regularization;
         'sgd' and 'adam' ignore it.  clip_grad_norm > 0: every gradient tensor is clipped to that norm
-        (slim's clip_gradient_norms); <= 0: off."""
+        (slim's clip_gradient_norms); <= 0: off.
+
+        unsupervised: no ground truth.  The batch holds batch / 2 pairs in both directions (slots 2k and 2k + 1) and the
+        loss is the occlusion-aware photometric loss of src/photometric.py at the five scales, with the supervised loss's
+        weights: psi = (|d| + 0.01)^photometric_q on the pixels that the forward-backward test (occ_alpha, occ_beta)
+        leaves.  Steps go through train_step_unsupervised / forward_backward_unsupervised."""
         self._set_optimizer(optimizer, momentum, min_momentum, max_momentum, weight_decay, clip_grad_norm, schedule)
         if dtype not in ("f32", "f16x2"):
             raise ValueError("trainer dtype must be 'f32' or 'f16x2'")
@@ -112,6 +118,20 @@ class FlowNetSTrainer:
         if self.hfem not in ("", "hard", "edges"):
             raise ValueError("add_hard_flow_mining must be '', 'hard' or 'edges'")
         self.lambda_w, self.hard_perc = float(lambda_weight), float(hard_examples_perc)
+        self.unsupervised, self._photo = bool(unsupervised), None
+        if self.unsupervised:
+            from .photometric import check_constants
+            # the models with two image inputs and the five-scale loss (FlowNet2's loss is single-scale, FlowNetS_interp's
+            # second input is no image)
+            if model not in ("FlowNetS", "FlowNetSD", "FlowNetC", "FlowNetCS", "FlowNetCSS"):
+                raise ValueError("unsupervised training covers FlowNetS, FlowNetSD, FlowNetC, FlowNetCS and FlowNetCSS, "
+                                 "not %s" % model)
+            if self.hfem:
+                raise ValueError("hard-flow-example mining needs a ground truth: not with unsupervised=True")
+            if batch % 2:
+                raise ValueError("unsupervised training runs every pair in both directions: batch must be even, got %d"
+                                 % batch)
+            self.occ_alpha, self.occ_beta, self.photometric_q = check_constants(occ_alpha, occ_beta, photometric_q)
         # label scale of the loss: 0.05 * gt for FlowNetS (flownet_s.py:123), 20 * gt for FlowNetSD (flownet_sd.py:122)
         self.gt_scale = 20.0 if model == "FlowNetSD" else 0.05
         # {prediction name: loss weight}: the five scales of FlowNetS.loss through compute_weighted_loss (weights / 5,
@@ -679,6 +699,7 @@ class FlowNetSTrainer:
         """Loss and all parameter gradients (left in self.grad_arena).  Returns the loss as a device scalar.
         reduce=True: every gradient bucket is all-reduced as soon as backward has produced it (overlap);
         finish with apply_gradients(reduced_world=...) / wait_reduction()."""
+        self._require_mode(False, "forward_backward")
         eng, s = self.eng, _hip.stream_ptr()
         self.gt.copy_(torch.as_tensor(gt_flow).to(dtype=torch.float32), non_blocking=True)
         eng.set_inputs(input_a, input_b)
@@ -702,7 +723,10 @@ class FlowNetSTrainer:
                                                                _hip.ptr(self._gbuf(pred)), _hip.ptr(self.loss_dev), n, h, w,
                                                                wgt, self.loss_scale, s))
             self.keep_label = (label, pw)
-        # ---- backward
+        return self._backward(s, reduce)
+
+    def _backward(self, s, reduce):
+        """The backward launches behind the loss gradients in the _gbufs; returns the loss scalar."""
         from .dist import allreduce_bucket_async
         self._pending, nb = [], 0
         for i, (name, ops) in enumerate(self.bwd_ops):
@@ -729,6 +753,8 @@ class FlowNetSTrainer:
             if g.data_ptr() not in self._no_zero:
                 _hip.check(lib.fn2_fill_zero(_hip.ptr(g), g.numel() * g.element_size(), s))
         _hip.check(lib.fn2_fill_zero(_hip.ptr(self.loss_dev), 4, s))
+        if self._photo is not None:  # the mask counts of the photometric loss
+            _hip.check(lib.fn2_fill_zero(_hip.ptr(self._photo.counts), self._photo.counts.numel() * 4, s))
 
     def wait_reduction(self):
         """Block the compute stream on the outstanding bucket all-reduces; returns the number of ranks summed."""
@@ -914,11 +940,91 @@ class FlowNetSTrainer:
         that contradicts that choice raises ValueError.
         FN2_TRAIN_GRAPH=0: the eager launch sequence."""
         import os
+        self._require_mode(False, "train_step")
         if not int(os.environ.get("FN2_TRAIN_GRAPH", "1")):
             loss = self.forward_backward(input_a, input_b, gt_flow, reduce=True, edges=edges)
             self.apply_gradients(reduced_world=self.wait_reduction())
             return loss
         return self._train_step_graph(input_a, input_b, gt_flow, edges)
+
+    # ------------------------------------------------------------------ unsupervised step
+    def _require_mode(self, unsupervised, what):
+        if self.unsupervised != unsupervised:
+            raise ValueError("%s belongs to %s trainer; this one was built with unsupervised=%s"
+                             % (what, "an unsupervised" if unsupervised else "a supervised", self.unsupervised))
+
+    def _alloc_photometric(self):
+        """Everything the photometric loss writes, allocated once and before any capture: per loss scale the frames at
+        that size and the mask, one mask count per scale, and the level table over them, the predictions and their
+        gradient buffers.  scale = (1 / gt_scale) * (w_l / W) turns a prediction into pixels of its level."""
+        if self._photo is not None:
+            return
+        from .photometric import level, level_table
+        new = lambda shape: torch.zeros(shape, dtype=torch.float32, device=self.dev)
+        ph = types.SimpleNamespace(names=list(self.loss_terms), imgs={}, masks={}, scales={},
+                                   counts=new((len(self.loss_terms),)))
+        levels = []
+        for i, (pname, wgt) in enumerate(self.loss_terms.items()):
+            pred = self.eng.outputs[pname]
+            n, h, w, _ = pred.shape
+            if self.H * w != self.W * h:
+                raise ValueError("unsupervised training needs one scale factor per level: %s is %dx%d for %dx%d frames"
+                                 % (pname, h, w, self.H, self.W))
+            ph.imgs[pname], ph.masks[pname] = new((n, h, w, 3)), new((n, h, w))
+            ph.scales[pname] = (1.0 / self.gt_scale) * (w / float(self.W))
+            levels.append(level(pred, ph.imgs[pname], ph.masks[pname], ph.counts[i:i + 1], self._gbuf(pred),
+                                ph.scales[pname], wgt))
+        ph.table = level_table(levels)
+        self._photo = ph
+
+    def _set_pairs(self, image_a, image_b):
+        """[P,H,W,3] frames of P = batch / 2 pairs into the engine's 2P slots, both directions (device copies)."""
+        from .photometric import interleave_pairs
+        dev = lambda x: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(
+            device=self.dev, dtype=torch.float32)
+        a, b = dev(image_a), dev(image_b)
+        want = (self.N // 2, self.H, self.W, 3)
+        if tuple(a.shape) != want or tuple(b.shape) != want:
+            raise ValueError("unsupervised step: frames must be %s (batch / 2 pairs), got %s and %s"
+                             % (want, tuple(a.shape), tuple(b.shape)))
+        interleave_pairs(a, b, self.eng.in_a, self.eng.in_b)
+
+    def _photometric_body(self, s):
+        """Behind the forward pass: the frames at the five sizes, then the masks and the loss with its gradients, one
+        launch each for all scales.  The gradients land in the _gbufs the supervised loss writes."""
+        lib, ph, eng = self.lib, self._photo, self.eng
+        for pname in ph.names:
+            img = ph.imgs[pname]
+            if min(img.shape[1:3]) == 1:
+                # no pixel of a 1-high or 1-wide level is valid (0 <= Y < h - 1 is empty), so its frames are never read;
+                # fn2_downsample_f32 has no size-1 output (the reference kernel divides by zero there)
+                continue
+            _hip.check(lib.fn2_downsample_f32(_hip.ptr(eng.in_a), _hip.ptr(img), self.N, self.H, self.W, 3,
+                                              int(img.shape[1]), int(img.shape[2]), s))
+        _hip.check(lib.fn2_photometric_masks(ph.table, len(ph.names), self.N, self.occ_alpha, self.occ_beta, s))
+        _hip.check(lib.fn2_photometric_loss_grad(ph.table, len(ph.names), self.N, self.photometric_q, self.loss_scale,
+                                                 _hip.ptr(self.loss_dev), s))
+
+    def forward_backward_unsupervised(self, image_a, image_b, reduce=False):
+        """forward_backward without a ground truth: image_a / image_b are [batch / 2, H, W, 3] frames in [0,1]; the
+        loss is the photometric one (left in self.loss_dev, returned), the gradients are left in self.grad_arena."""
+        self._require_mode(True, "forward_backward_unsupervised")
+        self._alloc_photometric()
+        s = _hip.stream_ptr()
+        self._set_pairs(image_a, image_b)
+        self._zero_buffers(s)
+        self.eng.launch()
+        self._photometric_body(s)
+        return self._backward(s, reduce)
+
+    def train_step_unsupervised(self, image_a, image_b):
+        """train_step without a ground truth, captured and replayed the same way (FN2_TRAIN_GRAPH=0: eager)."""
+        self._require_mode(True, "train_step_unsupervised")
+        if not int(os.environ.get("FN2_TRAIN_GRAPH", "1")):
+            loss = self.forward_backward_unsupervised(image_a, image_b, reduce=True)
+            self.apply_gradients(reduced_world=self.wait_reduction())
+            return loss
+        return self._train_step_graph(None, None, None, pairs=(image_a, image_b))
 
     # ------------------------------------------------------------------ captured step
     def _segment_body(self, seg):
@@ -930,9 +1036,11 @@ class FlowNetSTrainer:
         if seg == 0:
             self._zero_buffers(s)
             eng.launch()
+            if self.unsupervised:  # all scales at once; no labels, so the loop below has nothing to do
+                self._photometric_body(s)
             # (the label downsampling depends on the input only; as a parallel path beside the forward pass: 5.24 -> 5.29 ms,
             # its two graph edges cost more than the 0.15 ms of small launches they would hide)
-            for pname, wgt in self.loss_terms.items():
+            for pname, wgt in ({} if self.unsupervised else self.loss_terms).items():
                 pred = eng.outputs[pname]
                 n, h, w, _ = pred.shape
                 label = self._labels[pname]
@@ -1021,10 +1129,14 @@ class FlowNetSTrainer:
         from .dist import exchange_enabled
         # one segment per gradient bucket when the gradients are exchanged, else a single backward segment
         self._seg_ends = [i for i, _ in self.buckets] if exchange_enabled() else [len(self.bwd_ops) - 1]
-        self._labels = {pname: torch.empty_like(self.eng.outputs[pname]) for pname in self.loss_terms}
         for pname in self.loss_terms:
             self._gbuf(self.eng.outputs[pname])  # allocate outside the capture
-        self._alloc_mining(with_edges)
+        if self.unsupervised:
+            self._labels, self._mining = {}, None
+            self._alloc_photometric()
+        else:
+            self._labels = {pname: torch.empty_like(self.eng.outputs[pname]) for pname in self.loss_terms}
+            self._alloc_mining(with_edges)
         self._hyper = torch.zeros(5, dtype=torch.float32, device=self.dev)
         self._hyper_host = torch.zeros(5, dtype=torch.float32).pin_memory()
         self._build_adam_tables()
@@ -1049,7 +1161,7 @@ class FlowNetSTrainer:
         torch.cuda.current_stream().wait_stream(side)
         self._step_graphs = graphs
 
-    def _train_step_graph(self, input_a, input_b, gt_flow, edges=None):
+    def _train_step_graph(self, input_a, input_b, gt_flow, edges=None, pairs=None):
         from .dist import allreduce_bucket_async, exchange_enabled, world_size
         with_edges = self.hfem == "edges" and edges is not None
         if getattr(self, "_step_graphs", None) is None:
@@ -1059,8 +1171,11 @@ class FlowNetSTrainer:
                              % (("without", "with") if with_edges else ("with", "without")))
         if with_edges:
             self.edges_in.copy_(self._edges_dev(edges).reshape(self.edges_in.shape), non_blocking=True)
-        self.gt.copy_(torch.as_tensor(gt_flow).to(dtype=torch.float32), non_blocking=True)
-        self.eng.set_inputs(input_a, input_b)
+        if pairs is not None:  # the unsupervised step: frames into the slots, no ground truth
+            self._set_pairs(*pairs)
+        else:
+            self.gt.copy_(torch.as_tensor(gt_flow).to(dtype=torch.float32), non_blocking=True)
+            self.eng.set_inputs(input_a, input_b)
         world = world_size()
         self.step_count += 1
         if self._optim_entry:

@@ -644,6 +644,45 @@ typedef enum { FN2_MASK_F32 = 0, FN2_MASK_U8 = 1 } fn2_mask_dtype;
 int fn2_fb_occlusion(const float* flow_fw, const float* flow_bw, int64_t flow_pitch, int64_t flow_bstride, void* occ_fw,
                      void* occ_bw, int mask_dtype, int n, int h, int w, float alpha, float beta, void* stream);
 
+/* ---------------------------------------------------------------- occlusion-aware photometric loss (unsupervised training)
+ * The other half of the reference's SelFlow group, which it carries and never wires into a training graph:
+ *   fn2_photometric_masks      <- occlusion + tf_warp     src/utils.py:453-538  (the forward rule, per loss scale)
+ *   fn2_photometric_loss_grad  <- abs_robust_loss         src/utils.py:354-395  (loss_mean) of img - tf_warp(img', f),
+ *                                                         src/utils.py:453-515, and what autodiff of both yields
+ * The batch holds slots: image j is a frame and image j ^ 1 its partner (pair k: slots 2k and 2k + 1, the two directions),
+ * so n is even.  Per level, f = scale * pred in pixels of that level, the sample position is (x + f.u, y + f.v); product and
+ * sum are rounded separately, never fused.  tf_warp's index rules are those of fn2_tf_warp_f32 above; no tap leaves the
+ * image whatever pred holds.
+ *   mask = valid & ~occ as 0 / 1,  occ = |f + tf_warp(f', f)|^2 > alpha (|f|^2 + |tf_warp(f', f)|^2) + beta  (f' the
+ *          partner's scaled flow),  valid = 0 <= X < w - 1 and 0 <= Y < h - 1 (NaN fails): tf_warp returns exactly 0
+ *          where both taps of an axis clamp to one index, and such a pixel would count its own brightness as a residual
+ *   M    = sum mask over the level (an integer below 2^24: exact in any order)
+ *   L    = weight * sum_{j,y,x,c} mask * psi(d_c) / (2 M + 1e-6),  d_c = img[j] - tf_warp(img[j ^ 1], f)_c,
+ *          psi(d) = (|d| + 0.01)^q  (accurate powf)
+ *   dpred_u = grad_mult * weight * scale / (2 M + 1e-6) * mask * sum_c psi'(d_c) * (-d warp_c / dX),  dpred_v with d/dY;
+ *          psi'(d) = q (|d| + 0.01)^(q - 1) sign(d), sign(0) = 0;  d warp / dX = (y1 - Y)(Ic - Ia) + (Y - y0)(Id - Ib),
+ *          d warp / dY = (x1 - X)(Ib - Ia) + (X - x0)(Id - Ic) on tf_warp's clamped taps; mask and M are constants
+ *          (stop-gradient).  A level with M = 0 gives loss 0 and gradient 0.
+ * `levels` is a HOST array of 1..8 entries (no null pointer, h, w >= 1, h * w <= 2^30, pred / dpred 8-byte aligned); it
+ * travels to the kernel by value, so a captured graph keeps the table it was captured with, and all levels run in ONE
+ * launch.  No allocation, no host synchronisation. */
+typedef struct {
+  const float* pred; /* [n,h,w,2] fp32, dense */
+  const float* img;  /* [n,h,w,3] the frames at this level's size */
+  float* mask;       /* [n,h,w]   written by fn2_photometric_masks, read by fn2_photometric_loss_grad */
+  float* mask_sum;   /* one float: fn2_photometric_masks ADDS M into it (the caller zeroes it) */
+  float* dpred;      /* [n,h,w,2] stored by fn2_photometric_loss_grad */
+  int32_t h, w;
+  float scale;       /* prediction -> pixels of this level */
+  float weight;
+} fn2_photometric_level;
+int fn2_photometric_masks(const fn2_photometric_level* levels, int n_levels, int n, float alpha, float beta,
+                          void* stream);
+/* loss_accum += sum over the levels of L (one atomic per block and level); 0 < q <= 1 (the reference: 0.4); grad_mult
+ * as in fn2_epe_loss_grad. */
+int fn2_photometric_loss_grad(const fn2_photometric_level* levels, int n_levels, int n, float q, float grad_mult,
+                              float* loss_accum, void* stream);
+
 /* ---------------------------------------------------------------- launch-graph helpers (hipGraph) */
 int fn2_capture_begin(void* stream);
 int fn2_capture_end(void* stream, void** graph_exec);
