@@ -17,49 +17,10 @@
 // Both kernels take the table of levels by value and walk the levels one after another; within a level a wave owns 64
 // consecutive pixels of a row and the waves stride the (image, row, segment) units, as in occlusion.hip.  The scalars
 // are reduced by wave shuffles, then per level in LDS, and leave the block as one atomic per level.
-#include "tf_warp.h"
+#include "photo_levels.h"
 
 namespace fn2 {
 namespace {
-
-constexpr int PHOTO_BLOCK = 256;  // four waves, each on its own unit
-constexpr int PHOTO_WAVES = PHOTO_BLOCK / 64;
-constexpr int PHOTO_MAX_BLOCKS = 4096;
-constexpr int PHOTO_MAX_LEVELS = 8;
-
-struct PhotoArgs {
-  fn2_photometric_level lv[PHOTO_MAX_LEVELS];
-  int n_levels, n;
-};
-
-// f = scale * pred and the sample position, every product and every sum rounded on its own
-__device__ __forceinline__ float2 scaled_flow(float2 p, float s) {
-#pragma clang fp contract(off)
-  return make_float2(s * p.x, s * p.y);
-}
-__device__ __forceinline__ float coord(int p, float f) {
-#pragma clang fp contract(off)
-  return (float)p + f;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// the per-level partial sums of a block: every wave adds its own, then one global atomic per level that got something
-struct LevelSums {
-  float* s;
-  __device__ __forceinline__ void clear() {
-    if (threadIdx.x < PHOTO_MAX_LEVELS) s[threadIdx.x] = 0.f;
-    __syncthreads();
-  }
-  __device__ __forceinline__ void add(int level, float lane_part) {
-    const float v = wave_sum(lane_part);
-    if ((threadIdx.x & 63) == 0 && v != 0.f) atomicAdd(&s[level], v);
-  }
-};
 
 __global__ void __launch_bounds__(PHOTO_BLOCK) photometric_masks_kernel(const PhotoArgs a, float alpha, float beta) {
   __shared__ float sums[PHOTO_MAX_LEVELS];
@@ -174,8 +135,7 @@ int photo_args(const char* what, const fn2_photometric_level* levels, int n_leve
     FN2_REQUIRE(((reinterpret_cast<uintptr_t>(l.pred) | reinterpret_cast<uintptr_t>(l.dpred)) & 7) == 0,
                 "%s: level %d: pred and dpred must be 8-byte aligned", what, i);
     a.lv[i] = l;
-    const int64_t units = (int64_t)n * l.h * ((l.w + 63) / 64);
-    blocks = max(blocks, (units + PHOTO_WAVES - 1) / PHOTO_WAVES);
+    blocks = max(blocks, level_blocks(n, l));
   }
   grid = (int)min(blocks, (int64_t)PHOTO_MAX_BLOCKS);
   return FN2_OK;

@@ -116,6 +116,7 @@ PROTOTYPES = {
     "fn2_hfem_edge_weights": (_i, [_p, _f, _p, C.c_int64, _p]),
     "fn2_photometric_masks": (_i, [C.POINTER(Fn2PhotometricLevel), _i, _i, _f, _f, _p]),
     "fn2_photometric_loss_grad": (_i, [C.POINTER(Fn2PhotometricLevel), _i, _i, _f, _f, _p, _p]),
+    "fn2_smoothness_loss_grad": (_i, [C.POINTER(Fn2PhotometricLevel), _i, _i, _i, _f, _f, _f, _f, _i, _p, _p]),
     "fn2_leaky_bwd": (_i, [_tp, _tp, _p, _p]),
     "fn2_bias_grad": (_i, [_tp, _p, _p]),
     "fn2_gather_f32": (_i, [_p, _p, _p, C.c_int64, _p]),

@@ -30,6 +30,7 @@ FF_LIKE_RANGE = (65.0, 85.0)
 COLOUR_RANGES = {"d_brightness": (-51.0 / 255.0, 51.0 / 255.0), "f_saturation": (0.5, 1.5), "d_hue": (-0.2, 0.2),
                  "f_contrast": (0.2, 1.4)}
 MIN_PERCENTAGE = 0.01  # sample_from_distribution :514
+_COLOUR_WORDS = [COLOUR_ORDER, D_BRIGHTNESS, F_SATURATION, D_HUE, F_CONTRAST]
 
 _f32 = np.float32
 
@@ -166,16 +167,26 @@ def draw_validation_params(rng, n, height, width, invalid_like=1, num_distrib=2,
     return table
 
 
-def draw_estimation_params(rng, n, height=None, width=None, fast_mode=False):
+def draw_estimation_params(rng, n, height=None, width=None, fast_mode=False, shared_colour=False):
     """The tables of augment_all_estimation (dataloader.py:93-113): (table_a, table_b).  Flips and permutation are
-    shared (both tables carry them), each image has its own colour record."""
+    shared (both tables carry them), each image has its own colour record.
+
+    shared_colour (not in the reference; the 'pair' augmentation of unsupervised training): ONE colour record per sample,
+    copied into both tables, with f_contrast = 1.  Brightness, saturation and hue act on a pixel alone, so one record
+    maps equal pixels of the two frames to equal pixels; contrast is the one stage that reads a per-frame statistic (the
+    mean), and a shared factor around two different means would still shift one frame against the other -- factor 1
+    makes the stage the identity."""
     a, b = empty_params(n), empty_params(n)
     for ra, rb in zip(a, b):
         ra[FLIP_LR], ra[FLIP_UD] = rng.integers(0, 2, size=2)
         ra[PERM] = rng.integers(6)
         rb[[FLIP_LR, FLIP_UD, PERM]] = ra[[FLIP_LR, FLIP_UD, PERM]]
         _draw_colour(rng, ra, fast_mode)
-        _draw_colour(rng, rb, fast_mode)
+        if shared_colour:
+            ra.view(np.float32)[F_CONTRAST] = 1.0
+            rb[_COLOUR_WORDS] = ra[_COLOUR_WORDS]
+        else:
+            _draw_colour(rng, rb, fast_mode)
     return a, b
 
 
@@ -242,7 +253,6 @@ def _only(params, words):
 
 
 _SAMPLING_WORDS = list(range(DISTRIB, RECTS + 12))
-_COLOUR_WORDS = [COLOUR_ORDER, D_BRIGHTNESS, F_SATURATION, D_HUE, F_CONTRAST]
 
 
 def _rng(seed):

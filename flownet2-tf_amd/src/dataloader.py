@@ -4,7 +4,8 @@ text file listing `image_a image_b flow.flo` per line (the triples the TFRecords
 batched on the host, and the augmentation runs on the GPU through the preprocessing plugin's op surface (src/preprocessing.py):
 DataAugmentation on both images (image b inherits image a's transform), FlowAugmentation on the ground truth.
 The SelFlow-style augmentation the reference's loader itself applies (dataloader.py:35-113) is src/data_augmentation.py:
-`load_interp_batches(data_augmentation=True)` and `load_batches(augmentation='selflow')` switch it on.
+`load_interp_batches(data_augmentation=True)` and `load_batches(augmentation='selflow')` switch it on;
+`load_batches(augmentation='pair')` is its pair-consistent variant for the unsupervised loss.
 
 PREPROCESS values are the reference's FlyingChairs configuration (dataset_configs.py:60-157) as data.
 """
@@ -112,11 +113,14 @@ def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, dat
     augmentation the reference's live loader applies to image pairs instead of the plugin's (augment_all_estimation,
     dataloader.py:93-113 -> src/data_augmentation.py): flips, a channel permutation and a colour chain per image, no crop.
     ``allow_unlabeled`` (unsupervised training): a list file may hold `image_a image_b` lines, a third field is not read,
-    and the batches are (image_a, image_b, None); both augmentations transform a ground truth, so it needs
-    data_augmentation=False."""
-    if augmentation not in ("plugin", "selflow"):
-        raise ValueError("augmentation must be 'plugin' or 'selflow', got %r" % (augmentation,))
-    if allow_unlabeled and data_augmentation:
+    and the batches are (image_a, image_b, None); 'plugin' and 'selflow' transform a ground truth and recolour the frames
+    independently, so with them it needs data_augmentation=False.  ``augmentation='pair'`` is the one made for it (and fine
+    on labeled lists, whose flow is flipped as under 'selflow'): selflow's flips and channel permutation with ONE colour
+    record for both frames and no contrast stage (draw_estimation_params(shared_colour=True)), so equal pixels stay
+    equal."""
+    if augmentation not in ("plugin", "selflow", "pair"):
+        raise ValueError("augmentation must be 'plugin', 'selflow' or 'pair', got %r" % (augmentation,))
+    if allow_unlabeled and data_augmentation and augmentation != "pair":
         raise ValueError("allow_unlabeled needs data_augmentation=False: the augmentations transform a ground truth")
     rng = np.random.default_rng(seed)
     unlabeled = bool(allow_unlabeled) and not is_tfrecord(list_path)
@@ -140,9 +144,10 @@ def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, dat
             if not data_augmentation:
                 dev = lambda x: None if x is None else torch.from_numpy(x).to(P._hip.require_device())
                 yield dev(a), dev(b), dev(f)
-            elif augmentation == "selflow":
+            elif augmentation in ("selflow", "pair"):
                 from . import data_augmentation as DA
-                yield DA.augment_all_estimation(a, b, f, params=DA.draw_estimation_params(rng, len(a), fast_mode=fast_mode))
+                yield DA.augment_all_estimation(a, b, f, params=DA.draw_estimation_params(
+                    rng, len(a), fast_mode=fast_mode, shared_colour=augmentation == "pair"))
             else:
                 oa, ob, ta, itb = P.data_augmentation(
                     a, b, step, crop, a_cfg["name"], a_cfg["rand_type"], a_cfg["exp"], a_cfg["mean"], a_cfg["spread"],

@@ -1,14 +1,17 @@
 """python -m src.flownet_s.train --list train.txt --out ./logs [--steps N --batch 8 --checkpoint w.npz --dtype f16x2
                                  --ckpt-format npz|tf --training_schedule one_cycle --optimizer sgd|momentum|adamw
                                  --momentum M | --min_momentum A --max_momentum B --weight_decay D --clip_grad_norm C
-                                 --unsupervised --no-augment --photometric_q Q --occ_alpha A --occ_beta B]
+                                 --unsupervised --no-augment|--augmentation pair --photometric_q Q --occ_alpha A
+                                 --occ_beta B --smoothness_weight S --smoothness_order 1|2 --edge_lambda L]
 The reference's src/flownet_s/train.py:8-40 + Net.train (net.py:1002-1400) over the HIP trainer: FlyingChairs-style
 augmentation on the GPU, multiscale EPE loss, Adam on LONG_SCHEDULE (or the optimiser and schedule named), periodic
 .npz checkpoints under the reference's variable names.  Data: a list file of `image_a image_b flow.flo` triples (the
 reference's TFRecords are built from exactly these).  Under torch.distributed.run every rank trains on its own shuffling of the list (seed + rank) and
 the gradients are all-reduced (data parallel).
 --unsupervised: no ground truth is read (`image_a image_b` lines are accepted); every pair runs in both directions, so
---batch is even and batch / 2 pairs go in per step; the loss is the occlusion-aware photometric loss (src/photometric.py)."""
+--batch is even and batch / 2 pairs go in per step; the loss is the occlusion-aware photometric loss (src/photometric.py),
+with --smoothness_weight > 0 plus the edge-aware smoothness term (src/smoothness.py).  The one augmentation that keeps
+brightness constancy is --augmentation pair (flips, channel permutation and ONE colour record for both frames, no crop)."""
 import argparse
 import os
 import sys
@@ -118,24 +121,36 @@ def schedule_of(flags):
 def add_unsupervised_arguments(ap):
     ap.add_argument("--unsupervised", action="store_true",
                     help="train without ground truth on the occlusion-aware photometric loss: `image_a image_b` lines are "
-                         "accepted, --batch is even (batch / 2 pairs per step, both directions); needs --no-augment")
+                         "accepted, --batch is even (batch / 2 pairs per step, both directions); needs --no-augment or "
+                         "--augmentation pair")
     ap.add_argument("--photometric_q", type=float, default=0.4, help="exponent of the robust loss (|d| + 0.01)^q")
     ap.add_argument("--occ_alpha", type=float, default=0.01, help="forward-backward test: factor on the squared magnitudes")
     ap.add_argument("--occ_beta", type=float, default=0.5, help="forward-backward test: constant, in pixels^2 of the level")
+    ap.add_argument("--smoothness_weight", type=float, default=0.0,
+                    help="> 0: add the edge-aware smoothness term times this weight (untuned; 0, the default: off)")
+    ap.add_argument("--smoothness_order", type=int, default=1, help="1: first differences of the flow, 2: second differences")
+    ap.add_argument("--edge_lambda", type=float, default=150.0,
+                    help="edge weight exp(-edge_lambda * mean |frame difference|) of the smoothness term")
 
 
 def unsupervised_kwargs(flags):
     """The trainer's unsupervised arguments from parsed flags, checked before anything touches a device."""
     if not getattr(flags, "unsupervised", False):
         return {}
-    if getattr(flags, "augment", True):
+    if getattr(flags, "augment", True) and getattr(flags, "augmentation", "plugin") != "pair":
         raise ValueError("--unsupervised needs --no-augment: both augmentations recolour the two frames independently, "
                          "which breaks the brightness constancy the photometric loss assumes")
     if flags.batch % 2:
         raise ValueError("--unsupervised runs every pair in both directions: --batch must be even, got %d" % flags.batch)
     from ..photometric import check_constants
     alpha, beta, q = check_constants(flags.occ_alpha, flags.occ_beta, flags.photometric_q)
-    return dict(unsupervised=True, photometric_q=q, occ_alpha=alpha, occ_beta=beta)
+    kwargs = dict(unsupervised=True, photometric_q=q, occ_alpha=alpha, occ_beta=beta)
+    from ..smoothness import check_constants as check_smoothness
+    order, edge_lambda, _, weight = check_smoothness(getattr(flags, "smoothness_order", 1), getattr(flags, "edge_lambda", 150.0),
+                                                     1e-3, getattr(flags, "smoothness_weight", 0.0))
+    if weight > 0.0:  # (off: the trainer's own defaults, nothing handed on)
+        kwargs.update(smoothness_weight=weight, smoothness_order=order, edge_lambda=edge_lambda)
+    return kwargs
 
 
 def main(flags):
@@ -152,7 +167,7 @@ def main(flags):
     model = getattr(flags, "model", "FlowNetS")
     wts = W.load_weights(flags.checkpoint) if flags.checkpoint else W.init_weights(model, flags.seed)
     pre = FLYING_CHAIRS_PREPROCESS
-    augmentation = getattr(flags, "augmentation", "plugin")  # 'selflow' keeps the frame size: it has no crop
+    augmentation = getattr(flags, "augmentation", "plugin")  # 'selflow' and 'pair' keep the frame size: they have no crop
     h, w = ((pre["crop_height"], pre["crop_width"]) if flags.augment and augmentation == "plugin"
             else (flags.height, flags.width))
     schedule, train_params = schedule_of(flags)
@@ -213,10 +228,11 @@ def build_parser():
     ap.add_argument("--batch", type=int, default=8, help="pairs per GPU (the reference's FlyingChairs batch size)")
     ap.add_argument("--dtype", default="f16x2", choices=["f32", "f16x2"])
     ap.add_argument("--no-augment", dest="augment", action="store_false")
-    ap.add_argument("--augmentation", default="plugin", choices=["plugin", "selflow"],
+    ap.add_argument("--augmentation", default="plugin", choices=["plugin", "selflow", "pair"],
                     help="plugin (default): the Caffe-style DataAugmentation / FlowAugmentation ops with their crop; selflow: "
                          "what the reference's live loader applies to image pairs (augment_all_estimation: flips, channel "
-                         "permutation, colour chain per image; frames keep --height x --width)")
+                         "permutation, colour chain per image; frames keep --height x --width); pair: selflow's with one "
+                         "colour record for both frames and no contrast stage, the one --unsupervised accepts")
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--seed", type=int, default=1234)

@@ -66,7 +66,8 @@ class FlowNetSTrainer:
     def __init__(self, weights, batch, height, width, schedule=LONG_SCHEDULE, eps=1e-8, dtype="f32", model="FlowNetS",
                  add_hard_flow_mining="", lambda_weight=2.0, hard_examples_perc=50, optimizer="adam", momentum=None,
                  min_momentum=0.85, max_momentum=0.95, weight_decay=None, clip_grad_norm=-1.0, unsupervised=False,
-                 photometric_q=0.4, occ_alpha=0.01, occ_beta=0.5):
+                 photometric_q=0.4, occ_alpha=0.01, occ_beta=0.5, smoothness_weight=0.0, smoothness_order=1,
+                 edge_lambda=150.0, smoothness_eps=1e-3):
         """dtype 'f32': everything on the fp32 matrix cores.  'f16x2': activations, activation gradients and the
         weight copies the convolutions read are split fp16 (3 fp16 MFMAs per product, fp32 accumulate); the master
         weights, their gradients and the Adam state stay fp32.
@@ -80,7 +81,12 @@ class FlowNetSTrainer:
         unsupervised: no ground truth.  The batch holds batch / 2 pairs in both directions (slots 2k and 2k + 1) and the
         loss is the occlusion-aware photometric loss of src/photometric.py at the five scales, with the supervised loss's
         weights: psi = (|d| + 0.01)^photometric_q on the pixels that the forward-backward test (occ_alpha, occ_beta)
-        leaves.  Steps go through train_step_unsupervised / forward_backward_unsupervised."""
+        leaves.  Steps go through train_step_unsupervised / forward_backward_unsupervised.
+
+        smoothness_weight > 0 (unsupervised only): the edge-aware smoothness term of src/smoothness.py is added at the
+        five scales, times that weight and the scale's loss weight -- first or second differences of the flow
+        (smoothness_order) under sqrt(d^2 + smoothness_eps^2), weighted by exp(-edge_lambda * mean |frame difference|).
+        0 (default): the step launches what it launches without the argument."""
         self._set_optimizer(optimizer, momentum, min_momentum, max_momentum, weight_decay, clip_grad_norm, schedule)
         if dtype not in ("f32", "f16x2"):
             raise ValueError("trainer dtype must be 'f32' or 'f16x2'")
@@ -119,6 +125,11 @@ class FlowNetSTrainer:
             raise ValueError("add_hard_flow_mining must be '', 'hard' or 'edges'")
         self.lambda_w, self.hard_perc = float(lambda_weight), float(hard_examples_perc)
         self.unsupervised, self._photo = bool(unsupervised), None
+        from .smoothness import check_constants as check_smoothness
+        (self.smoothness_order, self.edge_lambda, self.smoothness_eps,
+         self.smoothness_weight) = check_smoothness(smoothness_order, edge_lambda, smoothness_eps, smoothness_weight)
+        if self.smoothness_weight and not self.unsupervised:
+            raise ValueError("smoothness_weight regularises the unsupervised loss: it needs unsupervised=True")
         if self.unsupervised:
             from .photometric import check_constants
             # the models with two image inputs and the five-scale loss (FlowNet2's loss is single-scale, FlowNetS_interp's
@@ -991,7 +1002,8 @@ class FlowNetSTrainer:
 
     def _photometric_body(self, s):
         """Behind the forward pass: the frames at the five sizes, then the masks and the loss with its gradients, one
-        launch each for all scales.  The gradients land in the _gbufs the supervised loss writes."""
+        launch each for all scales.  The gradients land in the _gbufs the supervised loss writes.  With a smoothness
+        weight one more launch over the same table adds that term to the loss and to the gradients."""
         lib, ph, eng = self.lib, self._photo, self.eng
         for pname in ph.names:
             img = ph.imgs[pname]
@@ -1004,6 +1016,10 @@ class FlowNetSTrainer:
         _hip.check(lib.fn2_photometric_masks(ph.table, len(ph.names), self.N, self.occ_alpha, self.occ_beta, s))
         _hip.check(lib.fn2_photometric_loss_grad(ph.table, len(ph.names), self.N, self.photometric_q, self.loss_scale,
                                                  _hip.ptr(self.loss_dev), s))
+        if self.smoothness_weight > 0.0:
+            _hip.check(lib.fn2_smoothness_loss_grad(ph.table, len(ph.names), self.N, self.smoothness_order,
+                                                    self.edge_lambda, self.smoothness_eps, self.smoothness_weight,
+                                                    self.loss_scale, 1, _hip.ptr(self.loss_dev), s))
 
     def forward_backward_unsupervised(self, image_a, image_b, reduce=False):
         """forward_backward without a ground truth: image_a / image_b are [batch / 2, H, W, 3] frames in [0,1]; the

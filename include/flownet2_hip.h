@@ -683,6 +683,32 @@ int fn2_photometric_masks(const fn2_photometric_level* levels, int n_levels, int
 int fn2_photometric_loss_grad(const fn2_photometric_level* levels, int n_levels, int n, float q, float grad_mult,
                               float* loss_accum, void* stream);
 
+/* ---------------------------------------------------------------- edge-aware smoothness term (unsupervised training)
+ * An ADDITION to the reference, which regularises its flow nowhere: the companion of the photometric loss above, over the
+ * same level table (it reads pred, img, dpred, h, w, scale, weight; mask and mask_sum are ignored and may be null).  n need
+ * not be even.  Per level, f = scale * pred rounded once as above, I = img, rho(d) = sqrt(d^2 + eps^2), rho'(d) = d / rho(d),
+ * k over the two flow components:
+ *   order 1   gx(y,x) = exp(-edge_lambda * (1/3) sum_c |I(y,x+1,c) - I(y,x,c)|),      x in [0, w - 2]
+ *             Dx_k(y,x) = f_k(y,x+1) - f_k(y,x),                                      Cx = n h (w - 1)
+ *   order 2   gx(y,x) = exp(-edge_lambda * (1/3) sum_c |I(y,x+1,c) - I(y,x-1,c)| / 2), x in [1, w - 2]
+ *             Dx_k(y,x) = f_k(y,x-1) - 2 f_k(y,x) + f_k(y,x+1),                       Cx = n h (w - 2)
+ *   Sx = sum_{j,y,x,k} gx rho(Dx_k);  gy, Dy, Sy, Cy the same along y
+ *   L  = weight * smooth_weight * 0.5 * (Sx / Cx + Sy / Cy); an axis too short for one term (w < order + 1, h < order + 1)
+ *        contributes 0, and a level with min(h, w) == 1 has loss 0 and gradient 0
+ *   dL/df_k(y,x), x part: order 1  (0.5 / Cx) (gx(x-1) rho'(Dx_k(x-1)) - gx(x) rho'(Dx_k(x)))
+ *                         order 2  (0.5 / Cx) (gx(x-1) rho'(Dx_k(x-1)) - 2 gx(x) rho'(Dx_k(x)) + gx(x+1) rho'(Dx_k(x+1)))
+ *        a term whose index lies outside its range is absent; the y part alike; I is a constant
+ *   dpred_k = grad_mult * weight * smooth_weight * scale * dL/df_k: stored (accumulate 0) or added to what dpred holds by a
+ *        plain load and store of the pixel's own element (accumulate 1).  The kernel gathers -- a pixel recomputes its
+ *        neighbours' terms -- so there is no atomic on dpred and the gradient is deterministic.
+ * loss_accum += sum over the levels of L (one atomic per block and level), not multiplied by grad_mult.  accurate expf and
+ * sqrtf.  No address depends on data: whatever pred holds, every load and store stays inside its level.  order 1 or 2;
+ * edge_lambda >= 0, eps > 0, smooth_weight >= 0, all finite; the table's rules are those above (1..8 levels, h, w >= 1,
+ * h * w <= 2^30, pred / dpred 8-byte aligned).  ONE launch for all levels; no allocation, no host synchronisation. */
+int fn2_smoothness_loss_grad(const fn2_photometric_level* levels, int n_levels, int n, int order, float edge_lambda,
+                             float eps, float smooth_weight, float grad_mult, int accumulate, float* loss_accum,
+                             void* stream);
+
 /* ---------------------------------------------------------------- launch-graph helpers (hipGraph) */
 int fn2_capture_begin(void* stream);
 int fn2_capture_end(void* stream, void** graph_exec);
