@@ -57,6 +57,11 @@ class Fn2PhotometricLevel(C.Structure):
                 ("dpred", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("scale", C.c_float), ("weight", C.c_float)]
 
 
+class Fn2SparseEpeLevel(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("label", C.c_void_p), ("dpred", C.c_void_p), ("count", C.c_void_p),
+                ("h", C.c_int32), ("w", C.c_int32), ("weight", C.c_float)]
+
+
 _i, _p, _f = C.c_int, C.c_void_p, C.c_float
 _ip = C.POINTER(C.c_int)
 _tp = C.POINTER(Fn2Tensor)
@@ -117,6 +122,8 @@ PROTOTYPES = {
     "fn2_photometric_masks": (_i, [C.POINTER(Fn2PhotometricLevel), _i, _i, _f, _f, _p]),
     "fn2_photometric_loss_grad": (_i, [C.POINTER(Fn2PhotometricLevel), _i, _i, _f, _f, _p, _p]),
     "fn2_smoothness_loss_grad": (_i, [C.POINTER(Fn2PhotometricLevel), _i, _i, _i, _f, _f, _f, _f, _i, _p, _p]),
+    "fn2_sparse_epe_count": (_i, [C.POINTER(Fn2SparseEpeLevel), _i, _i, _p]),
+    "fn2_sparse_epe_loss_grad": (_i, [C.POINTER(Fn2SparseEpeLevel), _i, _i, _f, _p, _p]),
     "fn2_leaky_bwd": (_i, [_tp, _tp, _p, _p]),
     "fn2_bias_grad": (_i, [_tp, _p, _p]),
     "fn2_gather_f32": (_i, [_p, _p, _p, C.c_int64, _p]),

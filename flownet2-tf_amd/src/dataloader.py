@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import preprocessing as P
-from .flowlib import read_flow
+from .flowlib import read_flow, read_sparse_flow
 
 
 def _p(rand_type, exp, mean, spread, prob=1.0):
@@ -70,14 +70,55 @@ def read_list(path, allow_unlabeled=False):
     return rows
 
 
-def _list_epoch(rows, rng, with_flow=True):
+def crop_window(shape, crop, mode, rng, name="sample"):
+    """(y0, x0) of the crop[0] x crop[1] window of a frame of shape[:2]: 'centre' (the one evaluate() cuts), or 'random'
+    with y0 then x0 drawn from `rng` (one draw each, also where only one position exists).  Pure host arithmetic."""
+    h, w = int(shape[0]), int(shape[1])
+    ch, cw = crop
+    if h < ch or w < cw:
+        raise ValueError("%s is %dx%d: smaller than the crop %dx%d" % (name, h, w, ch, cw))
+    if mode == "centre":
+        return (h - ch) // 2, (w - cw) // 2
+    return int(rng.integers(h - ch + 1)), int(rng.integers(w - cw + 1))
+
+
+def check_crop(crop, crop_mode):
+    """None, or (h, w) as two positive ints; crop_mode 'random' or 'centre'."""
+    if crop_mode not in ("random", "centre"):
+        raise ValueError("crop_mode must be 'random' or 'centre', got %r" % (crop_mode,))
+    if crop is None:
+        return None
+    try:
+        ch, cw = (int(v) for v in crop)
+    except (TypeError, ValueError):
+        raise ValueError("crop must be (height, width), got %r" % (crop,)) from None
+    if ch < 1 or cw < 1:
+        raise ValueError("crop must be (height, width) with both >= 1, got %r" % (crop,))
+    return ch, cw
+
+
+def _list_epoch(rows, rng, with_flow=True, sparse_gt=False, crop=None, crop_mode="random", crop_rng=None):
     """One epoch of (image_a, image_b, flow) host arrays from a list file, in a fresh random order; with_flow=False
-    leaves the ground truth unread (flow is None)."""
+    leaves the ground truth unread (flow is None).  sparse_gt reads the flow with read_sparse_flow (NaN where there is no
+    ground truth); crop cuts one window out of both frames and the flow."""
     from .net import imread
     for j in rng.permutation(len(rows)):
         r = rows[j]
-        yield (imread(r[0]).astype(np.float32) / 255.0, imread(r[1]).astype(np.float32) / 255.0,
-               read_flow(r[2]) if with_flow else None)
+        smp = (imread(r[0]).astype(np.float32) / 255.0, imread(r[1]).astype(np.float32) / 255.0,
+               (read_sparse_flow(r[2]) if sparse_gt else read_flow(r[2])) if with_flow else None)
+        if crop is not None:
+            smp = _crop_sample(smp, crop, crop_mode, crop_rng, r[0])
+        yield smp
+
+
+def _crop_sample(smp, crop, crop_mode, crop_rng, name):
+    """The same window of both frames and the flow."""
+    for x in smp[1:]:
+        if x is not None and x.shape[:2] != smp[0].shape[:2]:
+            raise ValueError("%s: the frames and the flow of a sample differ in size (%s, %s)"
+                             % (name, smp[0].shape[:2], x.shape[:2]))
+    y0, x0 = crop_window(smp[0].shape, crop, crop_mode, crop_rng, name)
+    return tuple(None if x is None else x[y0:y0 + crop[0], x0:x0 + crop[1]] for x in smp)
 
 
 def _tfrecord_epoch(path, rng, image_size, scale, shuffle_buffer):
@@ -104,7 +145,7 @@ def is_tfrecord(path):
 
 def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, data_augmentation=True, seed=0,
                  global_step=0, epochs=None, image_size=(384, 512), shuffle_buffer=256, augmentation="plugin",
-                 fast_mode=False, allow_unlabeled=False):
+                 fast_mode=False, allow_unlabeled=False, sparse_gt=False, crop=None, crop_mode="random"):
     """Generator of (image_a, image_b, flow) device tensors [B,h,w,3|3|2]; images in [0,1].  ``list_path`` is a
     text file of `image_a image_b flow.flo` triples or a ``.tfrecords`` file as the reference's converter writes it
     (``image_size`` = the dataset's PADDED_IMAGE_HEIGHT/WIDTH, dataset_configs.py:42-43).  With data_augmentation
@@ -117,19 +158,41 @@ def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, dat
     independently, so with them it needs data_augmentation=False.  ``augmentation='pair'`` is the one made for it (and fine
     on labeled lists, whose flow is flipped as under 'selflow'): selflow's flips and channel permutation with ONE colour
     record for both frames and no contrast stage (draw_estimation_params(shared_colour=True)), so equal pixels stay
-    equal."""
+    equal.
+    ``sparse_gt`` (KITTI, HD1K, Middlebury): the third field of a list file is read with flowlib.read_sparse_flow -- a KITTI
+    flow .png or a .flo with unknown pixels -- and the flow holds NaN where there is no ground truth.  'selflow' and 'pair'
+    move a flow pixel whole and flip by negation, so a NaN stays with its pixel; the plugin augmentation interpolates the
+    flow, where a NaN would spread, and is refused, as are .tfrecords files (their flow is dense).
+    ``crop=(h, w)``: every sample of a list file is cut to one host window -- both frames and the flow alike -- before it
+    is stacked, so frames of differing sizes (KITTI: 370..376 x 1224..1242) make one batch.  crop_mode 'random' draws the
+    window from a generator of its own, so the sample order and the augmentation draws are what they are without a crop;
+    'centre' is the window evaluate() cuts.  The plugin augmentation has its own crop and is refused."""
     if augmentation not in ("plugin", "selflow", "pair"):
         raise ValueError("augmentation must be 'plugin', 'selflow' or 'pair', got %r" % (augmentation,))
     if allow_unlabeled and data_augmentation and augmentation != "pair":
         raise ValueError("allow_unlabeled needs data_augmentation=False: the augmentations transform a ground truth")
+    crop = check_crop(crop, crop_mode)
+    plugin = bool(data_augmentation) and augmentation == "plugin"
+    if sparse_gt and plugin:
+        raise ValueError("sparse_gt does not go through the plugin augmentation (FlowAugmentation interpolates the flow and "
+                         "a NaN would spread): use data_augmentation=False, augmentation='selflow' or 'pair'")
+    if sparse_gt and is_tfrecord(list_path):
+        raise ValueError("sparse_gt reads list files; the flow of a .tfrecords file is dense")
+    if crop is not None and plugin:
+        raise ValueError("crop does not combine with the plugin augmentation, which has its own crop "
+                         "(preprocess['crop_height'], ['crop_width'])")
+    if crop is not None and is_tfrecord(list_path):
+        raise ValueError("crop cuts the samples of list files; the samples of a .tfrecords file share one size")
+    crop_rng = np.random.default_rng([int(seed), 0xC809]) if crop is not None and crop_mode == "random" else None
     rng = np.random.default_rng(seed)
     unlabeled = bool(allow_unlabeled) and not is_tfrecord(list_path)
     rows = None if is_tfrecord(list_path) else read_list(list_path, allow_unlabeled)
     a_cfg, b_cfg = config_to_arrays(preprocess["image_a"]), config_to_arrays(preprocess["image_b"])
-    crop = (preprocess["crop_height"], preprocess["crop_width"])
+    plugin_crop = (preprocess["crop_height"], preprocess["crop_width"])
     epoch, step = 0, int(global_step)
     while epochs is None or epoch < epochs:
-        source = _list_epoch(rows, rng, not unlabeled) if rows is not None else _tfrecord_epoch(
+        source = _list_epoch(rows, rng, not unlabeled, bool(sparse_gt), crop, crop_mode,
+                             crop_rng) if rows is not None else _tfrecord_epoch(
             list_path, rng, image_size, bool(preprocess.get("scale", False)), shuffle_buffer)
         pick = []
         produced = False
@@ -150,7 +213,7 @@ def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, dat
                     rng, len(a), fast_mode=fast_mode, shared_colour=augmentation == "pair"))
             else:
                 oa, ob, ta, itb = P.data_augmentation(
-                    a, b, step, crop, a_cfg["name"], a_cfg["rand_type"], a_cfg["exp"], a_cfg["mean"], a_cfg["spread"],
+                    a, b, step, plugin_crop, a_cfg["name"], a_cfg["rand_type"], a_cfg["exp"], a_cfg["mean"], a_cfg["spread"],
                     a_cfg["prob"], a_cfg["coeff_schedule"], b_cfg["name"], b_cfg["rand_type"], b_cfg["exp"], b_cfg["mean"],
                     b_cfg["spread"], b_cfg["prob"], b_cfg["coeff_schedule"], seed=int(rng.integers(1 << 31)))
                 if "noise" in preprocess["image_a"]:
@@ -160,7 +223,7 @@ def load_batches(list_path, batch_size, preprocess=FLYING_CHAIRS_PREPROCESS, dat
                     g = torch.Generator(device=oa.device).manual_seed(int(rng.integers(1 << 31)))
                     oa = (oa + sigma * torch.randn(oa.shape, generator=g, device=oa.device)).clamp_(0.0, 1.0)
                     ob = (ob + sigma * torch.randn(ob.shape, generator=g, device=ob.device)).clamp_(0.0, 1.0)
-                yield oa, ob, P.flow_augmentation(f, ta, itb, crop)
+                yield oa, ob, P.flow_augmentation(f, ta, itb, plugin_crop)
             step += 1
         if not produced:
             raise ValueError("%s holds fewer than one batch (%d) of samples" % (list_path, batch_size))

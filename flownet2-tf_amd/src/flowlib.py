@@ -34,6 +34,72 @@ def write_flow(flow, filename):
         flow.tofile(f)
 
 
+# ---------------------------------------------------------------------------------------------------
+# KITTI's flow format (reference src/flowlib.py: read_flow_png :103-123): a 16-bit RGB PNG holding
+# 64 u + 2^15, 64 v + 2^15 and a valid flag.  The codec is src/png16.py (zlib and struct alone).
+# ---------------------------------------------------------------------------------------------------
+def read_flow_png(path):
+    """KITTI flow .png -> (H, W, 3) float64 as the reference returns it: u and v = (x - 2^15) / 64, 0 where the third
+    channel is 0; the third channel as read."""
+    from .png16 import read_rgb16
+    flow = read_rgb16(path).astype(np.float64)
+    invalid = flow[:, :, 2] == 0
+    flow[:, :, 0:2] = (flow[:, :, 0:2] - 2 ** 15) / 64.0
+    flow[invalid, 0] = 0
+    flow[invalid, 1] = 0
+    return flow
+
+
+def write_flow_png(flow, path, valid=None):
+    """(H, W, 2) -> KITTI flow .png in the devkit's encoding: clip(64 f + 32768, 0, 65535) truncated to uint16, third channel
+    1 where `valid` (default: both components finite); invalid pixels are written as 0, 0, 0."""
+    from .png16 import write_rgb16
+    flow = np.asarray(flow, np.float64)
+    if flow.ndim != 3 or flow.shape[2] != 2:
+        raise ValueError("flow must be (H, W, 2)")
+    finite = np.isfinite(flow).all(axis=2)
+    valid = finite if valid is None else (np.asarray(valid).reshape(flow.shape[:2]).astype(bool) & finite)
+    out = np.zeros(flow.shape[:2] + (3,), np.uint16)
+    code = np.clip(64.0 * np.where(valid[..., None], flow, 0.0) + 32768.0, 0.0, 65535.0).astype(np.uint16)
+    out[..., :2] = np.where(valid[..., None], code, 0)
+    out[..., 2] = valid
+    write_rgb16(path, out)
+
+
+def read_sparse_flow(path):
+    """Ground truth that need not cover the frame -> (H, W, 2) float32 with NaN where there is none: a .png is KITTI's
+    format (NaN where its valid flag is 0), anything else a .flo whose unknown pixels (|u| or |v| above
+    UNKNOWN_FLOW_THRESH, the Middlebury convention) become NaN."""
+    if str(path).lower().endswith(".png"):
+        f = read_flow_png(path)
+        out = f[:, :, :2].astype(np.float32)
+        out[f[:, :, 2] == 0] = np.nan
+        return out
+    out = np.array(read_flow(path), np.float32)
+    with np.errstate(invalid="ignore"):
+        unknown = ~(np.abs(out) <= UNKNOWN_FLOW_THRESH).all(axis=2)  # (NaN fails <= too)
+    out[unknown] = np.nan
+    return out
+
+
+def kitti_metrics(est, gt, valid=None):
+    """{"epe", "fl_all", "valid_share"} of an estimate [..., 2] against a ground truth over the pixels where `valid`
+    (default: both ground-truth components finite): the mean endpoint error, and the share of those pixels that are
+    outliers by the KITTI devkit's rule -- epe > 3 px and epe > 5 % of the ground truth's magnitude.  Without a valid
+    pixel epe and fl_all are NaN and valid_share is 0."""
+    est, gt = np.asarray(est, np.float64), np.asarray(gt, np.float64)
+    finite = np.isfinite(gt).all(axis=-1)
+    valid = finite if valid is None else (np.asarray(valid).reshape(finite.shape).astype(bool) & finite)
+    m = int(valid.sum())
+    if m == 0:
+        return {"epe": float("nan"), "fl_all": float("nan"), "valid_share": 0.0}
+    d = est[valid] - gt[valid]
+    epe = np.sqrt((d * d).sum(axis=-1))
+    mag = np.sqrt((gt[valid] ** 2).sum(axis=-1))
+    return {"epe": float(epe.mean()), "fl_all": float(((epe > 3.0) & (epe > 0.05 * mag)).mean()),
+            "valid_share": m / float(valid.size)}
+
+
 def endpoint_error(flow, gt):
     """Mean end-point error over pixels whose ground truth is known (|gt| <= 1e9)."""
     flow = np.asarray(flow, np.float64)

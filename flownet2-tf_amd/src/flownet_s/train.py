@@ -2,7 +2,8 @@
                                  --ckpt-format npz|tf --training_schedule one_cycle --optimizer sgd|momentum|adamw
                                  --momentum M | --min_momentum A --max_momentum B --weight_decay D --clip_grad_norm C
                                  --unsupervised --no-augment|--augmentation pair --photometric_q Q --occ_alpha A
-                                 --occ_beta B --smoothness_weight S --smoothness_order 1|2 --edge_lambda L]
+                                 --occ_beta B --smoothness_weight S --smoothness_order 1|2 --edge_lambda L
+                                 --sparse_gt --crop]
 The reference's src/flownet_s/train.py:8-40 + Net.train (net.py:1002-1400) over the HIP trainer: FlyingChairs-style
 augmentation on the GPU, multiscale EPE loss, Adam on LONG_SCHEDULE (or the optimiser and schedule named), periodic
 .npz checkpoints under the reference's variable names.  Data: a list file of `image_a image_b flow.flo` triples (the
@@ -11,7 +12,11 @@ the gradients are all-reduced (data parallel).
 --unsupervised: no ground truth is read (`image_a image_b` lines are accepted); every pair runs in both directions, so
 --batch is even and batch / 2 pairs go in per step; the loss is the occlusion-aware photometric loss (src/photometric.py),
 with --smoothness_weight > 0 plus the edge-aware smoothness term (src/smoothness.py).  The one augmentation that keeps
-brightness constancy is --augmentation pair (flips, channel permutation and ONE colour record for both frames, no crop)."""
+brightness constancy is --augmentation pair (flips, channel permutation and ONE colour record for both frames, no crop).
+--sparse_gt: the third field of a line is a KITTI flow .png (or a .flo with unknown pixels); pixels without ground truth take
+no part in the loss (src/sparse_epe.py) and validation prints EPE and Fl-all over the valid pixels.  --crop cuts a random
+--height x --width window out of every sample (the centre window of validation samples), so frames of differing sizes make
+one batch; both need --no-augment or --augmentation selflow|pair."""
 import argparse
 import os
 import sys
@@ -153,8 +158,42 @@ def unsupervised_kwargs(flags):
     return kwargs
 
 
+def add_sparse_arguments(ap):
+    ap.add_argument("--sparse_gt", action="store_true",
+                    help="sparse ground truth (KITTI flow .png, or .flo with unknown pixels): pixels without a label take no "
+                         "part in the loss; needs --no-augment or --augmentation selflow|pair; not with --unsupervised")
+    ap.add_argument("--crop", action="store_true",
+                    help="cut a random --height x --width window out of every training sample (the centre window of "
+                         "--val-list samples); needs --no-augment or --augmentation selflow|pair")
+
+
+def sparse_kwargs(flags):
+    """(trainer arguments, loader arguments) of --sparse_gt and --crop from parsed flags, checked before anything touches
+    a device."""
+    sparse, crop = bool(getattr(flags, "sparse_gt", False)), bool(getattr(flags, "crop", False))
+    plugin = getattr(flags, "augment", True) and getattr(flags, "augmentation", "plugin") == "plugin"
+    if sparse and getattr(flags, "unsupervised", False):
+        raise ValueError("--sparse_gt is a supervised loss: not with --unsupervised")
+    if sparse and plugin:
+        raise ValueError("--sparse_gt needs --no-augment or --augmentation selflow|pair: the plugin augmentation "
+                         "interpolates the flow, and a pixel without ground truth would spread")
+    if sparse and getattr(flags, "model", "FlowNetS") in ("FlowNetS_interp", "FlowNet2"):
+        raise ValueError("--sparse_gt covers FlowNetS, FlowNetSD, FlowNetC, FlowNetCS and FlowNetCSS")
+    if crop and plugin:
+        raise ValueError("--crop needs --no-augment or --augmentation selflow|pair: the plugin augmentation has its own crop")
+    if crop and (flags.height < 1 or flags.width < 1):
+        raise ValueError("--crop takes a --height x --width window: both must be >= 1")
+    loader = {}
+    if sparse:
+        loader["sparse_gt"] = True
+    if crop:
+        loader["crop"] = (flags.height, flags.width)
+    return (dict(sparse_gt=True) if sparse else {}), loader
+
+
 def main(flags):
     unsup = unsupervised_kwargs(flags)
+    sparse, loader_kw = sparse_kwargs(flags)
     import torch
     from .. import weights as W
     from ..trainer import FlowNetSTrainer
@@ -172,7 +211,7 @@ def main(flags):
             else (flags.height, flags.width))
     schedule, train_params = schedule_of(flags)
     tr = FlowNetSTrainer(wts, flags.batch, h, w, schedule=schedule, dtype=flags.dtype, model=model,
-                         **optimizer_kwargs(flags), **unsup)
+                         **optimizer_kwargs(flags), **unsup, **sparse)
     tr.train_params = train_params
     if flags.checkpoint:  # Adam moments + global_step, when the checkpoint carries them (ours and the reference's do)
         state = load_full_checkpoint(flags.checkpoint)
@@ -186,7 +225,7 @@ def main(flags):
     pairs = flags.batch // 2 if unsup else flags.batch  # (an unsupervised step fills two slots per pair)
     for step, (a, b, f) in enumerate(load_batches(flags.list, pairs, pre, flags.augment, seed=flags.seed + rank,
                                                   global_step=step0, augmentation=augmentation,
-                                                  allow_unlabeled=bool(unsup)), step0 + 1):
+                                                  allow_unlabeled=bool(unsup), **loader_kw), step0 + 1):
         loss = tr.train_step_unsupervised(a, b) if unsup else tr.train_step(a, b, f)
         if step % flags.log_every == 0 or step == end:
             val = float(loss.item()) + (tr.l2_term() if flags.report_l2 else 0.0)
@@ -201,9 +240,14 @@ def main(flags):
             # validation frames come at their own size (--height/--width or the list's); the trainer's engine is built
             # at the training size (the augmentation crop when --augment): evaluate() centre-crops larger frames to it
             vb = load_batches(flags.val_list, flags.batch, pre, False, seed=0, epochs=1,
-                              image_size=(flags.height, flags.width))
-            print("global step %6d | validation EPE %.4f px" % (step, tr.evaluate(vb, getattr(flags, "val_batches", None))),
-                  flush=True)
+                              image_size=(flags.height, flags.width), **dict(loader_kw, crop_mode="centre"))
+            if sparse:
+                m = tr.evaluate_sparse(vb, getattr(flags, "val_batches", None))
+                print("global step %6d | validation EPE %.4f px | Fl-all %.2f %%" % (step, m["epe"], 100.0 * m["fl_all"]),
+                      flush=True)
+            else:
+                print("global step %6d | validation EPE %.4f px" % (step, tr.evaluate(vb, getattr(flags, "val_batches", None))),
+                      flush=True)
         if rank == 0 and save:
             save_checkpoint(flags.out, step, dict(unpack_weights(tr), **tr.optimizer_state()), flags.ckpt_format,
                             stem=model.lower().replace("net", "net_"))
@@ -245,6 +289,7 @@ def build_parser():
     add_schedule_arguments(ap)
     add_optimizer_arguments(ap)
     add_unsupervised_arguments(ap)
+    add_sparse_arguments(ap)
     return ap
 
 

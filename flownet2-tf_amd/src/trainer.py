@@ -67,7 +67,7 @@ class FlowNetSTrainer:
                  add_hard_flow_mining="", lambda_weight=2.0, hard_examples_perc=50, optimizer="adam", momentum=None,
                  min_momentum=0.85, max_momentum=0.95, weight_decay=None, clip_grad_norm=-1.0, unsupervised=False,
                  photometric_q=0.4, occ_alpha=0.01, occ_beta=0.5, smoothness_weight=0.0, smoothness_order=1,
-                 edge_lambda=150.0, smoothness_eps=1e-3):
+                 edge_lambda=150.0, smoothness_eps=1e-3, sparse_gt=False):
         """dtype 'f32': everything on the fp32 matrix cores.  'f16x2': activations, activation gradients and the
         weight copies the convolutions read are split fp16 (3 fp16 MFMAs per product, fp32 accumulate); the master
         weights, their gradients and the Adam state stay fp32.
@@ -86,7 +86,21 @@ class FlowNetSTrainer:
         smoothness_weight > 0 (unsupervised only): the edge-aware smoothness term of src/smoothness.py is added at the
         five scales, times that weight and the scale's loss weight -- first or second differences of the flow
         (smoothness_order) under sqrt(d^2 + smoothness_eps^2), weighted by exp(-edge_lambda * mean |frame difference|).
-        0 (default): the step launches what it launches without the argument."""
+        0 (default): the step launches what it launches without the argument.
+
+        sparse_gt: the ground truth does not cover the frame (KITTI, HD1K, Middlebury): a pixel whose u or v is not finite
+        carries no label.  The labels stay the five NaN-aware downsamples; the loss behind them is src/sparse_epe.py's --
+        every scale normalised by its own count of valid label pixels, gradient exactly 0 where there is none -- in two
+        launches for all scales.  FlowNetS, FlowNetSD, FlowNetC and the last network of FlowNetCS / FlowNetCSS.  False
+        (default): the step launches what it launches without the argument."""
+        self.sparse_gt, self._sparse = bool(sparse_gt), None
+        if self.sparse_gt:  # before anything else is built
+            if unsupervised:
+                raise ValueError("sparse_gt is a supervised loss: not with unsupervised=True")
+            if add_hard_flow_mining:
+                raise ValueError("sparse_gt does not combine with hard-flow-example mining")
+            if model in ("FlowNetS_interp", "FlowNet2"):
+                raise ValueError("sparse_gt covers FlowNetS, FlowNetSD, FlowNetC, FlowNetCS and FlowNetCSS, not %s" % model)
         self._set_optimizer(optimizer, momentum, min_momentum, max_momentum, weight_decay, clip_grad_norm, schedule)
         if dtype not in ("f32", "f16x2"):
             raise ValueError("trainer dtype must be 'f32' or 'f16x2'")
@@ -714,9 +728,14 @@ class FlowNetSTrainer:
         eng, s = self.eng, _hip.stream_ptr()
         self.gt.copy_(torch.as_tensor(gt_flow).to(dtype=torch.float32), non_blocking=True)
         eng.set_inputs(input_a, input_b)
+        if self.sparse_gt:
+            self._alloc_sparse()  # (before the zeroing: it owns the counters)
         self._zero_buffers(s)
         eng.launch()
         # ---- loss and its gradient at the five scales (flownet_s.py:122-158)
+        if self.sparse_gt:
+            self._sparse_body(s)
+            return self._backward(s, reduce)
         edges_dev = None if edges is None else self._edges_dev(edges)
         for pname, wgt in self.loss_terms.items():
             pred = eng.outputs[pname]
@@ -766,6 +785,8 @@ class FlowNetSTrainer:
         _hip.check(lib.fn2_fill_zero(_hip.ptr(self.loss_dev), 4, s))
         if self._photo is not None:  # the mask counts of the photometric loss
             _hip.check(lib.fn2_fill_zero(_hip.ptr(self._photo.counts), self._photo.counts.numel() * 4, s))
+        if self._sparse is not None:  # the valid-label counts of the sparse loss
+            _hip.check(lib.fn2_fill_zero(_hip.ptr(self._sparse.counts), self._sparse.counts.numel() * 4, s))
 
     def wait_reduction(self):
         """Block the compute stream on the outstanding bucket all-reduces; returns the number of ranks summed."""
@@ -1042,6 +1063,74 @@ class FlowNetSTrainer:
             return loss
         return self._train_step_graph(None, None, None, pairs=(image_a, image_b))
 
+    # ------------------------------------------------------------------ sparse ground truth
+    def _alloc_sparse(self):
+        """Everything the sparse loss writes, allocated once and before any capture: the labels of the five scales, one
+        counter of valid label pixels per scale, and the level table over them, the predictions and their gradient
+        buffers."""
+        if self._sparse is not None:
+            return
+        from .sparse_epe import level, level_table
+        sp = types.SimpleNamespace(names=list(self.loss_terms),
+                                   counts=torch.zeros(len(self.loss_terms), dtype=torch.int32, device=self.dev))
+        self._labels = {pname: torch.empty_like(self.eng.outputs[pname]) for pname in self.loss_terms}
+        sp.table = level_table([level(self.eng.outputs[p], self._labels[p], self._gbuf(self.eng.outputs[p]),
+                                      sp.counts[i:i + 1], wgt) for i, (p, wgt) in enumerate(self.loss_terms.items())])
+        self._sparse = sp
+
+    def _sparse_body(self, s):
+        """Behind the forward pass: the labels as the dense loss forms them -- scale * NaN is NaN, and the downsample skips
+        NaN samples and returns NaN where more than half of the weight was NaN -- then the valid counts and the loss with
+        its gradients, one launch each for all scales.  The gradients land in the _gbufs the dense loss writes."""
+        lib, sp = self.lib, self._sparse
+        for pname in sp.names:
+            n, h, w, _ = self.eng.outputs[pname].shape
+            _hip.check(lib.fn2_downsample_scaled_f32(_hip.ptr(self.gt), self.gt_scale, _hip.ptr(self._labels[pname]), n,
+                                                     self.H, self.W, 2, h, w, s))
+        _hip.check(lib.fn2_sparse_epe_count(sp.table, len(sp.names), self.N, s))
+        _hip.check(lib.fn2_sparse_epe_loss_grad(sp.table, len(sp.names), self.N, self.loss_scale, _hip.ptr(self.loss_dev), s))
+
+    def evaluate_sparse(self, batches, max_batches=None):
+        """evaluate() for sparse ground truth: forward-only over (image_a, image_b, gt_flow) batches with the current
+        weights, the full-resolution `flow` output scored over the pixels whose ground truth is finite.  Returns
+        {"epe": mean endpoint error in pixels, "fl_all": share of those pixels with an error above 3 px AND above 5 % of
+        the ground truth's magnitude (the KITTI devkit's outlier rule), "valid_share": valid pixels / all pixels}; epe and
+        fl_all are NaN when no pixel is valid."""
+        err = torch.zeros((), dtype=torch.float64, device=self.dev)
+        bad = torch.zeros((), dtype=torch.float64, device=self.dev)
+        valid_n, total_n = torch.zeros((), dtype=torch.float64, device=self.dev), 0
+
+        def crop(x):  # the centre crop of evaluate()
+            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+            h, w = int(t.shape[1]), int(t.shape[2])
+            if (h, w) == (self.H, self.W):
+                return t
+            if h < self.H or w < self.W:
+                raise ValueError("validation frames %dx%d are smaller than the trainer's %dx%d" % (h, w, self.H, self.W))
+            y0, x0 = (h - self.H) // 2, (w - self.W) // 2
+            return t[:, y0:y0 + self.H, x0:x0 + self.W]
+
+        for i, (a, b, gt) in enumerate(batches):
+            if max_batches is not None and i >= max_batches:
+                break
+            a, b, gt = crop(a), crop(b), crop(gt)
+            self.eng.set_inputs(a, b)
+            self.eng.launch()
+            gt_dev = gt.to(device=self.dev, dtype=torch.float32)
+            valid = torch.isfinite(gt_dev).all(dim=3)
+            gt0 = torch.where(valid[..., None], gt_dev, torch.zeros_like(gt_dev))
+            d = self.eng.outputs["flow"] - gt0
+            e = torch.sqrt((d * d).sum(dim=3))
+            mag = torch.sqrt((gt0 * gt0).sum(dim=3))
+            err += torch.where(valid, e, torch.zeros_like(e)).double().sum()
+            bad += (valid & (e > 3.0) & (e > 0.05 * mag)).double().sum()
+            valid_n += valid.double().sum()
+            total_n += valid.numel()
+        m = float(valid_n.item())
+        nan = float("nan")
+        return {"epe": float(err.item()) / m if m else nan, "fl_all": float(bad.item()) / m if m else nan,
+                "valid_share": m / total_n if total_n else 0.0}
+
     # ------------------------------------------------------------------ captured step
     def _segment_body(self, seg):
         """Launches of segment `seg` on torch's current stream.  Segment 0 starts with the zeroing, the forward and
@@ -1056,7 +1145,9 @@ class FlowNetSTrainer:
                 self._photometric_body(s)
             # (the label downsampling depends on the input only; as a parallel path beside the forward pass: 5.24 -> 5.29 ms,
             # its two graph edges cost more than the 0.15 ms of small launches they would hide)
-            for pname, wgt in ({} if self.unsupervised else self.loss_terms).items():
+            if self.sparse_gt:
+                self._sparse_body(s)
+            for pname, wgt in ({} if self.unsupervised or self.sparse_gt else self.loss_terms).items():
                 pred = eng.outputs[pname]
                 n, h, w, _ = pred.shape
                 label = self._labels[pname]
@@ -1150,6 +1241,9 @@ class FlowNetSTrainer:
         if self.unsupervised:
             self._labels, self._mining = {}, None
             self._alloc_photometric()
+        elif self.sparse_gt:
+            self._mining = None
+            self._alloc_sparse()
         else:
             self._labels = {pname: torch.empty_like(self.eng.outputs[pname]) for pname in self.loss_terms}
             self._alloc_mining(with_edges)

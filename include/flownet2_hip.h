@@ -709,6 +709,43 @@ int fn2_smoothness_loss_grad(const fn2_photometric_level* levels, int n_levels, 
                              float eps, float smooth_weight, float grad_mult, int accumulate, float* loss_accum,
                              void* stream);
 
+/* ---------------------------------------------------------------- multi-scale EPE over sparse ground truth (KITTI)
+ * The supervised loss for ground truth that does not cover the frame (KITTI, HD1K, Middlebury).  A label pixel whose u or
+ * v is not finite carries no ground truth: that is what the reference's Downsample op (fn2_downsample_f32 /
+ * fn2_downsample_scaled_f32 above) hands on -- it skips NaN samples and returns NaN where more than half of the weight was
+ * NaN, the Caffe FlowNet2 convention for sparse labels -- and what average_endpoint_error (utils.py:209-224) cannot take.
+ * Per level:
+ *   valid(p) = both label components finite (fabsf(x) < inf: NaN and +-inf fail)
+ *   M     = #valid over the batch (an integer: atomics are exact in any order)
+ *   e     = ||pred - label||_2 in fp32, as fn2_epe_loss_grad forms it
+ *   L     = weight * (h w) * sum_valid e / M, ADDED to *loss_accum, not multiplied by grad_mult
+ *   dpred = grad_mult * weight * (h w) / M * (pred - label) / e on valid pixels with e > 0, and exactly +0.0f in both
+ *           components at every other pixel: invalid ones, e == 0, and e NaN (which fails e > 0 as in fn2_epe_loss_grad)
+ *   M = 0: loss 0 and an all-zero dpred
+ * weight * h * w / M is formed in double and rounded once.  With every label finite M = n h w and the definition is
+ * average_endpoint_error, weight / n * sum e: the sparse loss is the dense one at full validity.
+ * M counts the valid pixels of THIS process's batch: under data parallelism every rank normalises by its own M and the
+ * all-reduce averages the gradients as before (ranks are not weighted by their share of valid pixels).
+ * `levels` is a HOST array of 1..8 entries; it travels to the kernel by value, so a captured graph keeps the table it was
+ * captured with.  Each entry point is ONE launch for all levels; no allocation, no host synchronisation.  No address
+ * depends on data: whatever pred and label hold, every load and store stays inside its level.  Rules: non-null table
+ * and pointers, n >= 1, h, w >= 1, n * h * w < 2^31, pred / label / dpred 8-byte and count 4-byte aligned, weight finite
+ * and >= 0, grad_mult finite and > 0. */
+typedef struct {
+  const float* pred;   /* [n,h,w,2] fp32, dense, 8-byte aligned */
+  const float* label;  /* [n,h,w,2]; a pixel whose u or v is not finite carries no ground truth */
+  float* dpred;        /* [n,h,w,2] stored (never accumulated), 8-byte aligned */
+  uint32_t* count;     /* one counter: fn2_sparse_epe_count ADDS M into it (the caller zeroes it) */
+  int32_t h, w;
+  float weight;
+} fn2_sparse_epe_level;
+/* count += M per level (one atomic per block and level); reads label only. */
+int fn2_sparse_epe_count(const fn2_sparse_epe_level* levels, int n_levels, int n, void* stream);
+/* Reads the counters fn2_sparse_epe_count filled; loss_accum += sum over the levels of L (one atomic per block and
+ * level); grad_mult as in fn2_epe_loss_grad. */
+int fn2_sparse_epe_loss_grad(const fn2_sparse_epe_level* levels, int n_levels, int n, float grad_mult,
+                             float* loss_accum, void* stream);
+
 /* ---------------------------------------------------------------- launch-graph helpers (hipGraph) */
 int fn2_capture_begin(void* stream);
 int fn2_capture_end(void* stream, void** graph_exec);
