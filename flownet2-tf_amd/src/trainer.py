@@ -24,7 +24,7 @@ import types
 import numpy as np
 import torch
 
-from . import _hip, weights as W
+from . import _hip, loss_stages, weights as W
 from .engine import Engine, _round_up
 from .training_schedules import LONG_SCHEDULE
 
@@ -93,7 +93,7 @@ class FlowNetSTrainer:
         every scale normalised by its own count of valid label pixels, gradient exactly 0 where there is none -- in two
         launches for all scales.  FlowNetS, FlowNetSD, FlowNetC and the last network of FlowNetCS / FlowNetCSS.  False
         (default): the step launches what it launches without the argument."""
-        self.sparse_gt, self._sparse = bool(sparse_gt), None
+        self.sparse_gt = bool(sparse_gt)
         if self.sparse_gt:  # before anything else is built
             if unsupervised:
                 raise ValueError("sparse_gt is a supervised loss: not with unsupervised=True")
@@ -138,7 +138,7 @@ class FlowNetSTrainer:
         if self.hfem not in ("", "hard", "edges"):
             raise ValueError("add_hard_flow_mining must be '', 'hard' or 'edges'")
         self.lambda_w, self.hard_perc = float(lambda_weight), float(hard_examples_perc)
-        self.unsupervised, self._photo = bool(unsupervised), None
+        self.unsupervised = bool(unsupervised)
         from .smoothness import check_constants as check_smoothness
         (self.smoothness_order, self.edge_lambda, self.smoothness_eps,
          self.smoothness_weight) = check_smoothness(smoothness_order, edge_lambda, smoothness_eps, smoothness_weight)
@@ -180,6 +180,8 @@ class FlowNetSTrainer:
         self.keep = []
         self.gt = torch.zeros((batch, height, width, 2), dtype=torch.float32, device=self.dev)
         self.loss_dev = torch.zeros(1, dtype=torch.float32, device=self.dev)
+        # the loss stages built so far by "with an edge map" ('edges' mode only), the latest step's, the captured step's
+        self._stages, self._stage, self._captured = {}, None, None
         self._build()
 
     # ------------------------------------------------------------------ construction
@@ -681,14 +683,16 @@ class FlowNetSTrainer:
         from .training_schedules import learning_rate
         return learning_rate(self.schedule, step, getattr(self, "train_params", None))
 
+    def _f32(self, x):
+        """A tensor or array as a fp32 device tensor."""
+        return (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(device=self.dev, dtype=torch.float32)
+
     def _pack_interp(self, input_a, matches_a, sparse_flow):
         """FlowNetS_interp: the tower's second 'image' is [0.05 * sparse_flow | matches] (flownet_s_interp.py:34-38)."""
-        dev = lambda x: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(
-            device=self.dev, dtype=torch.float32)
-        m = dev(matches_a)
+        m = self._f32(matches_a)
         if m.ndim == 3:
             m = m[..., None]
-        return dev(input_a), torch.cat([dev(sparse_flow) * 0.05, m], dim=3)
+        return self._f32(input_a), torch.cat([self._f32(sparse_flow) * 0.05, m], dim=3)
 
     def forward_backward_interp(self, input_a, matches_a, sparse_flow, gt_flow, edges=None, reduce=False):
         """forward_backward on the packed inputs of FlowNetS_interp (_pack_interp)."""
@@ -700,59 +704,49 @@ class FlowNetSTrainer:
         a, b = self._pack_interp(input_a, matches_a, sparse_flow)
         return self.train_step(a, b, gt_flow, edges=edges)
 
-    def _pixel_weights(self, pred, label, edges_dev):
-        """Per-pixel loss weights of the mining modes on the eager path (None for plain AEPE), one level per call: the
-        exact top-k selection of 'hard' (fn2_hfem_hard_weights) or 1 + lambda * downsampled edges."""
-        if self.hfem == "hard":
-            from .losses import hard_example_weights
-            return hard_example_weights(label, pred, self.hard_perc, self.lambda_w).reshape(-1)
-        if self.hfem == "edges" and edges_dev is not None:
-            from .downsample import downsample
-            e = downsample(edges_dev, [pred.shape[1], pred.shape[2]])
-            wgt = torch.empty(e.numel(), dtype=torch.float32, device=e.device)
-            _hip.check(self.lib.fn2_hfem_edge_weights(_hip.ptr(e), self.lambda_w, _hip.ptr(wgt), e.numel(), _hip.stream_ptr()))
-            return wgt
-        return None
+    # the loss state by the names its readers know: that kind's stage or None, the latest labels, the captured mode
+    _photo = property(lambda self: next((st for st in self._stages.values() if st.kind == "photometric"), None))
+    _sparse = property(lambda self: next((st for st in self._stages.values() if st.kind == "sparse"), None))
+    _labels = property(lambda self: self._stage.labels)
+    _mining = property(lambda self: self._captured.kind if self._captured.kind in ("hard", "edges") else None)
 
-    def _edges_dev(self, edges):
-        """An edge map given as [N,H,W] or [N,H,W,1], as a fp32 [N,H,W,1] device tensor."""
-        e = (edges if isinstance(edges, torch.Tensor) else torch.as_tensor(np.asarray(edges))).to(
-            device=self.dev, dtype=torch.float32)
-        return e[..., None] if e.ndim == 3 else e
+    def _pick_stage(self, edges, captured=False):
+        """The loss stage (src/loss_stages.py) of this call, built on first use and allocated: before the zeroing and before
+        any capture.  'edges' without an edge map is plain AEPE; the captured step stays with its first call's choice."""
+        with_map = self.hfem == "edges" and edges is not None
+        if captured and self._captured is not None and self._captured is not self._stages.get(with_map):
+            raise ValueError("train_step: the captured step was built %s an edge map; this call is %s one"
+                             % (("without", "with") if with_map else ("with", "without")))
+        if with_map not in self._stages:
+            self._stages[with_map] = loss_stages.stage_for(self, with_map)
+        stage = self._stage = self._stages[with_map]
+        stage.alloc()
+        if with_map:  # [N,H,W] or [N,H,W,1] into the stage's static input
+            stage.edges_in.copy_(self._f32(edges).reshape(stage.edges_in.shape), non_blocking=True)
+        return stage
+
+    def _set_inputs(self, input_a, input_b, gt_flow):
+        """The step's inputs: frame pairs in both directions (no ground truth), else two inputs and the ground truth."""
+        if self.unsupervised:
+            return self._set_pairs(input_a, input_b)
+        self.gt.copy_(torch.as_tensor(gt_flow).to(dtype=torch.float32), non_blocking=True)
+        self.eng.set_inputs(input_a, input_b)
 
     def forward_backward(self, input_a, input_b, gt_flow, reduce=False, edges=None):
         """Loss and all parameter gradients (left in self.grad_arena).  Returns the loss as a device scalar.
         reduce=True: every gradient bucket is all-reduced as soon as backward has produced it (overlap);
         finish with apply_gradients(reduced_world=...) / wait_reduction()."""
         self._require_mode(False, "forward_backward")
-        eng, s = self.eng, _hip.stream_ptr()
-        self.gt.copy_(torch.as_tensor(gt_flow).to(dtype=torch.float32), non_blocking=True)
-        eng.set_inputs(input_a, input_b)
-        if self.sparse_gt:
-            self._alloc_sparse()  # (before the zeroing: it owns the counters)
-        self._zero_buffers(s)
-        eng.launch()
-        # ---- loss and its gradient at the five scales (flownet_s.py:122-158)
-        if self.sparse_gt:
-            self._sparse_body(s)
-            return self._backward(s, reduce)
-        edges_dev = None if edges is None else self._edges_dev(edges)
-        for pname, wgt in self.loss_terms.items():
-            pred = eng.outputs[pname]
-            n, h, w, _ = pred.shape
-            label = torch.empty_like(pred)
-            # labels: downsample(gt_scale * gt) -- the scaling (flownet_s.py:123) happens per sample inside the op
-            _hip.check(self.lib.fn2_downsample_scaled_f32(_hip.ptr(self.gt), self.gt_scale, _hip.ptr(label), n, self.H, self.W,
-                                                          2, h, w, s))
-            pw = self._pixel_weights(pred, label, edges_dev) if self.hfem else None
-            if pw is None:
-                _hip.check(self.lib.fn2_epe_loss_grad(_hip.ptr(pred), _hip.ptr(label), _hip.ptr(self._gbuf(pred)),
-                                                      _hip.ptr(self.loss_dev), n, h, w, wgt, self.loss_scale, s))
-            else:
-                _hip.check(self.lib.fn2_epe_loss_grad_weighted(_hip.ptr(pred), _hip.ptr(label), _hip.ptr(pw),
-                                                               _hip.ptr(self._gbuf(pred)), _hip.ptr(self.loss_dev), n, h, w,
-                                                               wgt, self.loss_scale, s))
-            self.keep_label = (label, pw)
+        return self._forward_backward(input_a, input_b, gt_flow, edges, reduce)
+
+    def _forward_backward(self, input_a, input_b, gt_flow, edges, reduce):
+        """The eager step up to the gradients: inputs, zeroing, forward, the loss stage, backward."""
+        s = _hip.stream_ptr()
+        self._set_inputs(input_a, input_b, gt_flow)
+        stage = self._pick_stage(edges)
+        self._zero_buffers(s, stage)
+        self.eng.launch()
+        stage.launch(s)
         return self._backward(s, reduce)
 
     def _backward(self, s, reduce):
@@ -774,19 +768,17 @@ class FlowNetSTrainer:
                 nb += 1
         return self.loss_dev
 
-    def _zero_buffers(self, s):
+    def _zero_buffers(self, s, stage):
         """Zero what the step accumulates into: the flat parameter-gradient arena, the activation-gradient buffers whose
-        first writer adds (the others are stored into, _plan_zeroing) and the loss scalar -- memset nodes on the stream."""
+        first writer adds (the others are stored into, _plan_zeroing), the loss scalar, stage.zeroed -- memset nodes."""
         lib = self.lib
         _hip.check(lib.fn2_fill_zero(_hip.ptr(self.grad_arena), self.grad_arena.numel() * 4, s))
         for g in self.gbufs.values():
             if g.data_ptr() not in self._no_zero:
                 _hip.check(lib.fn2_fill_zero(_hip.ptr(g), g.numel() * g.element_size(), s))
         _hip.check(lib.fn2_fill_zero(_hip.ptr(self.loss_dev), 4, s))
-        if self._photo is not None:  # the mask counts of the photometric loss
-            _hip.check(lib.fn2_fill_zero(_hip.ptr(self._photo.counts), self._photo.counts.numel() * 4, s))
-        if self._sparse is not None:  # the valid-label counts of the sparse loss
-            _hip.check(lib.fn2_fill_zero(_hip.ptr(self._sparse.counts), self._sparse.counts.numel() * 4, s))
+        for buf in stage.zeroed:
+            _hip.check(lib.fn2_fill_zero(_hip.ptr(buf), buf.numel() * buf.element_size(), s))
 
     def wait_reduction(self):
         """Block the compute stream on the outstanding bucket all-reduces; returns the number of ranks summed."""
@@ -823,34 +815,31 @@ class FlowNetSTrainer:
         self.refresh_backward_weights(forward=False)
 
     # ------------------------------------------------------------------ validation
+    def _crop(self, x):
+        """Centre crop of a [N,H,W,C] batch to the engine's size (validation frames are not augmented, so they arrive
+        at the dataset's size while the engine has the augmentation crop's, dataloader.FLYING_CHAIRS_PREPROCESS)."""
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        h, w = int(t.shape[1]), int(t.shape[2])
+        if (h, w) == (self.H, self.W):
+            return t
+        if h < self.H or w < self.W:
+            raise ValueError("validation frames %dx%d are smaller than the trainer's %dx%d" % (h, w, self.H, self.W))
+        y0, x0 = (h - self.H) // 2, (w - self.W) // 2
+        return t[:, y0:y0 + self.H, x0:x0 + self.W]
+
     def evaluate(self, batches, max_batches=None):
         """Forward-only pass over an iterable of (image_a, image_b, gt_flow) device batches with the CURRENT weights:
         mean endpoint error of the full-resolution `flow` output against the ground truth, in pixels -- the validation
         the reference interleaves with training (Net.train's custom train_step_fn, net.py:1300-1380: every
         `valid_iters` steps, average EPE over the validation batches)."""
-        total, count = 0.0, 0
-
-        def crop(x):
-            """Centre crop of a [N,H,W,C] batch to the engine's size (validation frames are not augmented, so they
-            arrive at the dataset's size while the engine has the augmentation crop's, dataloader.FLYING_CHAIRS_PREPROCESS)."""
-            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-            h, w = int(t.shape[1]), int(t.shape[2])
-            if (h, w) == (self.H, self.W):
-                return t
-            if h < self.H or w < self.W:
-                raise ValueError("validation frames %dx%d are smaller than the trainer's %dx%d" % (h, w, self.H, self.W))
-            y0, x0 = (h - self.H) // 2, (w - self.W) // 2
-            return t[:, y0:y0 + self.H, x0:x0 + self.W]
-
+        total, count, crop = 0.0, 0, self._crop
         for i, (a, b, gt) in enumerate(batches):
             if max_batches is not None and i >= max_batches:
                 break
             a, b, gt = crop(a), crop(b), crop(gt)
             self.eng.set_inputs(a, b)
             self.eng.launch()
-            gt_dev = (gt if isinstance(gt, torch.Tensor) else torch.as_tensor(np.asarray(gt))).to(
-                device=self.dev, dtype=torch.float32)
-            d = self.eng.outputs["flow"] - gt_dev
+            d = self.eng.outputs["flow"] - self._f32(gt)
             total += float(torch.sqrt((d * d).sum(dim=3)).mean().item())
             count += 1
         return total / max(count, 1)
@@ -971,13 +960,16 @@ class FlowNetSTrainer:
         is fixed by the first captured step ('edges' without a map is plain AEPE, as on the eager path): a later step
         that contradicts that choice raises ValueError.
         FN2_TRAIN_GRAPH=0: the eager launch sequence."""
-        import os
         self._require_mode(False, "train_step")
-        if not int(os.environ.get("FN2_TRAIN_GRAPH", "1")):
-            loss = self.forward_backward(input_a, input_b, gt_flow, reduce=True, edges=edges)
-            self.apply_gradients(reduced_world=self.wait_reduction())
-            return loss
-        return self._train_step_graph(input_a, input_b, gt_flow, edges)
+        return self._step(input_a, input_b, gt_flow, edges)
+
+    def _step(self, input_a, input_b, gt_flow, edges=None):
+        """train_step* behind their mode checks: the captured step, or with FN2_TRAIN_GRAPH=0 the eager sequence."""
+        if int(os.environ.get("FN2_TRAIN_GRAPH", "1")):
+            return self._train_step_graph(input_a, input_b, gt_flow, edges)
+        loss = self._forward_backward(input_a, input_b, gt_flow, edges, reduce=True)
+        self.apply_gradients(reduced_world=self.wait_reduction())
+        return loss
 
     # ------------------------------------------------------------------ unsupervised step
     def _require_mode(self, unsupervised, what):
@@ -985,111 +977,28 @@ class FlowNetSTrainer:
             raise ValueError("%s belongs to %s trainer; this one was built with unsupervised=%s"
                              % (what, "an unsupervised" if unsupervised else "a supervised", self.unsupervised))
 
-    def _alloc_photometric(self):
-        """Everything the photometric loss writes, allocated once and before any capture: per loss scale the frames at
-        that size and the mask, one mask count per scale, and the level table over them, the predictions and their
-        gradient buffers.  scale = (1 / gt_scale) * (w_l / W) turns a prediction into pixels of its level."""
-        if self._photo is not None:
-            return
-        from .photometric import level, level_table
-        new = lambda shape: torch.zeros(shape, dtype=torch.float32, device=self.dev)
-        ph = types.SimpleNamespace(names=list(self.loss_terms), imgs={}, masks={}, scales={},
-                                   counts=new((len(self.loss_terms),)))
-        levels = []
-        for i, (pname, wgt) in enumerate(self.loss_terms.items()):
-            pred = self.eng.outputs[pname]
-            n, h, w, _ = pred.shape
-            if self.H * w != self.W * h:
-                raise ValueError("unsupervised training needs one scale factor per level: %s is %dx%d for %dx%d frames"
-                                 % (pname, h, w, self.H, self.W))
-            ph.imgs[pname], ph.masks[pname] = new((n, h, w, 3)), new((n, h, w))
-            ph.scales[pname] = (1.0 / self.gt_scale) * (w / float(self.W))
-            levels.append(level(pred, ph.imgs[pname], ph.masks[pname], ph.counts[i:i + 1], self._gbuf(pred),
-                                ph.scales[pname], wgt))
-        ph.table = level_table(levels)
-        self._photo = ph
-
     def _set_pairs(self, image_a, image_b):
         """[P,H,W,3] frames of P = batch / 2 pairs into the engine's 2P slots, both directions (device copies)."""
         from .photometric import interleave_pairs
-        dev = lambda x: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(
-            device=self.dev, dtype=torch.float32)
-        a, b = dev(image_a), dev(image_b)
+        a, b = self._f32(image_a), self._f32(image_b)
         want = (self.N // 2, self.H, self.W, 3)
         if tuple(a.shape) != want or tuple(b.shape) != want:
             raise ValueError("unsupervised step: frames must be %s (batch / 2 pairs), got %s and %s"
                              % (want, tuple(a.shape), tuple(b.shape)))
         interleave_pairs(a, b, self.eng.in_a, self.eng.in_b)
 
-    def _photometric_body(self, s):
-        """Behind the forward pass: the frames at the five sizes, then the masks and the loss with its gradients, one
-        launch each for all scales.  The gradients land in the _gbufs the supervised loss writes.  With a smoothness
-        weight one more launch over the same table adds that term to the loss and to the gradients."""
-        lib, ph, eng = self.lib, self._photo, self.eng
-        for pname in ph.names:
-            img = ph.imgs[pname]
-            if min(img.shape[1:3]) == 1:
-                # no pixel of a 1-high or 1-wide level is valid (0 <= Y < h - 1 is empty), so its frames are never read;
-                # fn2_downsample_f32 has no size-1 output (the reference kernel divides by zero there)
-                continue
-            _hip.check(lib.fn2_downsample_f32(_hip.ptr(eng.in_a), _hip.ptr(img), self.N, self.H, self.W, 3,
-                                              int(img.shape[1]), int(img.shape[2]), s))
-        _hip.check(lib.fn2_photometric_masks(ph.table, len(ph.names), self.N, self.occ_alpha, self.occ_beta, s))
-        _hip.check(lib.fn2_photometric_loss_grad(ph.table, len(ph.names), self.N, self.photometric_q, self.loss_scale,
-                                                 _hip.ptr(self.loss_dev), s))
-        if self.smoothness_weight > 0.0:
-            _hip.check(lib.fn2_smoothness_loss_grad(ph.table, len(ph.names), self.N, self.smoothness_order,
-                                                    self.edge_lambda, self.smoothness_eps, self.smoothness_weight,
-                                                    self.loss_scale, 1, _hip.ptr(self.loss_dev), s))
-
     def forward_backward_unsupervised(self, image_a, image_b, reduce=False):
         """forward_backward without a ground truth: image_a / image_b are [batch / 2, H, W, 3] frames in [0,1]; the
         loss is the photometric one (left in self.loss_dev, returned), the gradients are left in self.grad_arena."""
         self._require_mode(True, "forward_backward_unsupervised")
-        self._alloc_photometric()
-        s = _hip.stream_ptr()
-        self._set_pairs(image_a, image_b)
-        self._zero_buffers(s)
-        self.eng.launch()
-        self._photometric_body(s)
-        return self._backward(s, reduce)
+        return self._forward_backward(image_a, image_b, None, None, reduce)
 
     def train_step_unsupervised(self, image_a, image_b):
         """train_step without a ground truth, captured and replayed the same way (FN2_TRAIN_GRAPH=0: eager)."""
         self._require_mode(True, "train_step_unsupervised")
-        if not int(os.environ.get("FN2_TRAIN_GRAPH", "1")):
-            loss = self.forward_backward_unsupervised(image_a, image_b, reduce=True)
-            self.apply_gradients(reduced_world=self.wait_reduction())
-            return loss
-        return self._train_step_graph(None, None, None, pairs=(image_a, image_b))
+        return self._step(image_a, image_b, None)
 
     # ------------------------------------------------------------------ sparse ground truth
-    def _alloc_sparse(self):
-        """Everything the sparse loss writes, allocated once and before any capture: the labels of the five scales, one
-        counter of valid label pixels per scale, and the level table over them, the predictions and their gradient
-        buffers."""
-        if self._sparse is not None:
-            return
-        from .sparse_epe import level, level_table
-        sp = types.SimpleNamespace(names=list(self.loss_terms),
-                                   counts=torch.zeros(len(self.loss_terms), dtype=torch.int32, device=self.dev))
-        self._labels = {pname: torch.empty_like(self.eng.outputs[pname]) for pname in self.loss_terms}
-        sp.table = level_table([level(self.eng.outputs[p], self._labels[p], self._gbuf(self.eng.outputs[p]),
-                                      sp.counts[i:i + 1], wgt) for i, (p, wgt) in enumerate(self.loss_terms.items())])
-        self._sparse = sp
-
-    def _sparse_body(self, s):
-        """Behind the forward pass: the labels as the dense loss forms them -- scale * NaN is NaN, and the downsample skips
-        NaN samples and returns NaN where more than half of the weight was NaN -- then the valid counts and the loss with
-        its gradients, one launch each for all scales.  The gradients land in the _gbufs the dense loss writes."""
-        lib, sp = self.lib, self._sparse
-        for pname in sp.names:
-            n, h, w, _ = self.eng.outputs[pname].shape
-            _hip.check(lib.fn2_downsample_scaled_f32(_hip.ptr(self.gt), self.gt_scale, _hip.ptr(self._labels[pname]), n,
-                                                     self.H, self.W, 2, h, w, s))
-        _hip.check(lib.fn2_sparse_epe_count(sp.table, len(sp.names), self.N, s))
-        _hip.check(lib.fn2_sparse_epe_loss_grad(sp.table, len(sp.names), self.N, self.loss_scale, _hip.ptr(self.loss_dev), s))
-
     def evaluate_sparse(self, batches, max_batches=None):
         """evaluate() for sparse ground truth: forward-only over (image_a, image_b, gt_flow) batches with the current
         weights, the full-resolution `flow` output scored over the pixels whose ground truth is finite.  Returns
@@ -1098,25 +1007,14 @@ class FlowNetSTrainer:
         fl_all are NaN when no pixel is valid."""
         err = torch.zeros((), dtype=torch.float64, device=self.dev)
         bad = torch.zeros((), dtype=torch.float64, device=self.dev)
-        valid_n, total_n = torch.zeros((), dtype=torch.float64, device=self.dev), 0
-
-        def crop(x):  # the centre crop of evaluate()
-            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-            h, w = int(t.shape[1]), int(t.shape[2])
-            if (h, w) == (self.H, self.W):
-                return t
-            if h < self.H or w < self.W:
-                raise ValueError("validation frames %dx%d are smaller than the trainer's %dx%d" % (h, w, self.H, self.W))
-            y0, x0 = (h - self.H) // 2, (w - self.W) // 2
-            return t[:, y0:y0 + self.H, x0:x0 + self.W]
-
+        valid_n, total_n, crop = torch.zeros((), dtype=torch.float64, device=self.dev), 0, self._crop
         for i, (a, b, gt) in enumerate(batches):
             if max_batches is not None and i >= max_batches:
                 break
             a, b, gt = crop(a), crop(b), crop(gt)
             self.eng.set_inputs(a, b)
             self.eng.launch()
-            gt_dev = gt.to(device=self.dev, dtype=torch.float32)
+            gt_dev = self._f32(gt)
             valid = torch.isfinite(gt_dev).all(dim=3)
             gt0 = torch.where(valid[..., None], gt_dev, torch.zeros_like(gt_dev))
             d = self.eng.outputs["flow"] - gt0
@@ -1139,25 +1037,9 @@ class FlowNetSTrainer:
         eng, s = self.eng, _hip.stream_ptr()
         nseg = len(self._seg_ends)
         if seg == 0:
-            self._zero_buffers(s)
+            self._zero_buffers(s, self._captured)
             eng.launch()
-            if self.unsupervised:  # all scales at once; no labels, so the loop below has nothing to do
-                self._photometric_body(s)
-            # (the label downsampling depends on the input only; as a parallel path beside the forward pass: 5.24 -> 5.29 ms,
-            # its two graph edges cost more than the 0.15 ms of small launches they would hide)
-            if self.sparse_gt:
-                self._sparse_body(s)
-            for pname, wgt in ({} if self.unsupervised or self.sparse_gt else self.loss_terms).items():
-                pred = eng.outputs[pname]
-                n, h, w, _ = pred.shape
-                label = self._labels[pname]
-                _hip.check(self.lib.fn2_downsample_scaled_f32(_hip.ptr(self.gt), self.gt_scale, _hip.ptr(label), n, self.H,
-                                                              self.W, 2, h, w, s))
-                if self._mining is None:
-                    _hip.check(self.lib.fn2_epe_loss_grad(_hip.ptr(pred), _hip.ptr(label), _hip.ptr(self._gbuf(pred)),
-                                                          _hip.ptr(self.loss_dev), n, h, w, wgt, self.loss_scale, s))
-            if self._mining is not None:
-                self._mining_body(s)
+            self._captured.launch(s)
         if seg < nseg:
             lo = 0 if seg == 0 else self._seg_ends[seg - 1] + 1
             # (the filter gradients as a parallel path of the graph -- they need only the layer's finished output
@@ -1176,47 +1058,6 @@ class FlowNetSTrainer:
                                                     _hip.ptr(self._adam_l2), len(self.params), _hip.ptr(self._hyper), s))
         self.refresh_backward_weights(forward=False)
 
-    def _alloc_mining(self, with_edges):
-        """Everything the mining losses of the captured step write, allocated before the capture: per loss scale the
-        endpoint-error and weight maps and, for 'edges', the downsampled edge map, plus the static input self.edges_in.
-        self._mining: None (plain AEPE: also 'edges' without an edge map), 'hard' or 'edges'."""
-        from .losses import hard_k, hard_weight_of, hfem_level
-        self._mining = self.hfem if self.hfem == "hard" or (self.hfem == "edges" and with_edges) else None
-        if self._mining is None:
-            return
-        new = lambda shape: torch.zeros(shape, dtype=torch.float32, device=self.dev)
-        self._hfem_weight = {p: new(self.eng.outputs[p].shape[:3]) for p in self.loss_terms}
-        if self._mining == "edges":
-            self.edges_in = new((self.N, self.H, self.W, 1))
-            self._edge_maps = {p: new(tuple(self.eng.outputs[p].shape[:3]) + (1,)) for p in self.loss_terms}
-            return
-        self._hfem_epe = {p: new(self.eng.outputs[p].shape[:3]) for p in self.loss_terms}
-        levels = []
-        for p in self.loss_terms:
-            numel = self._hfem_epe[p].numel()
-            k = hard_k(numel, self.hard_perc)
-            levels.append(hfem_level(self.eng.outputs[p], self._labels[p], self._hfem_epe[p], self._hfem_weight[p], k,
-                                     hard_weight_of(numel, k, self.lambda_w)))
-        self._hfem_levels = (_hip.Fn2HfemLevel * len(levels))(*levels)
-
-    def _mining_body(self, s):
-        """Segment 0 behind the labels: the pixel weights of every scale ('hard': one launch for all of them), then the
-        weighted loss and its gradient per scale."""
-        lib = self.lib
-        if self._mining == "hard":
-            _hip.check(lib.fn2_hfem_hard_weights(self._hfem_levels, len(self._hfem_levels), s))
-        for pname, wgt in self.loss_terms.items():
-            pred = self.eng.outputs[pname]
-            n, h, w, _ = pred.shape
-            pw = self._hfem_weight[pname]
-            if self._mining == "edges":
-                e = self._edge_maps[pname]
-                _hip.check(lib.fn2_downsample_f32(_hip.ptr(self.edges_in), _hip.ptr(e), n, self.H, self.W, 1, h, w, s))
-                _hip.check(lib.fn2_hfem_edge_weights(_hip.ptr(e), self.lambda_w, _hip.ptr(pw), pw.numel(), s))
-            _hip.check(lib.fn2_epe_loss_grad_weighted(_hip.ptr(pred), _hip.ptr(self._labels[pname]), _hip.ptr(pw),
-                                                      _hip.ptr(self._gbuf(pred)), _hip.ptr(self.loss_dev), n, h, w, wgt,
-                                                      self.loss_scale, s))
-
     def _build_adam_tables(self):
         """{w, m, v, g, split-fp16 forward copy of w (or 0), its scale} per parameter tensor (fn2_adam_step_multi): Adam
         rewrites the copy the forward convolutions read while it has the new master in registers."""
@@ -1232,21 +1073,11 @@ class FlowNetSTrainer:
         self._adam_counts = torch.tensor([p["n"] for p in self.params], dtype=torch.int64, device=self.dev)
         self._adam_l2 = torch.tensor([l2 if p["reg"] else 0.0 for p in self.params], dtype=torch.float32, device=self.dev)
 
-    def _capture_step(self, with_edges=False):
+    def _capture_step(self, stage):
         from .dist import exchange_enabled
         # one segment per gradient bucket when the gradients are exchanged, else a single backward segment
         self._seg_ends = [i for i, _ in self.buckets] if exchange_enabled() else [len(self.bwd_ops) - 1]
-        for pname in self.loss_terms:
-            self._gbuf(self.eng.outputs[pname])  # allocate outside the capture
-        if self.unsupervised:
-            self._labels, self._mining = {}, None
-            self._alloc_photometric()
-        elif self.sparse_gt:
-            self._mining = None
-            self._alloc_sparse()
-        else:
-            self._labels = {pname: torch.empty_like(self.eng.outputs[pname]) for pname in self.loss_terms}
-            self._alloc_mining(with_edges)
+        self._captured = stage  # (allocated, and with it the _gbufs of the predictions: nothing is allocated in the capture)
         self._hyper = torch.zeros(5, dtype=torch.float32, device=self.dev)
         self._hyper_host = torch.zeros(5, dtype=torch.float32).pin_memory()
         self._build_adam_tables()
@@ -1271,21 +1102,12 @@ class FlowNetSTrainer:
         torch.cuda.current_stream().wait_stream(side)
         self._step_graphs = graphs
 
-    def _train_step_graph(self, input_a, input_b, gt_flow, edges=None, pairs=None):
+    def _train_step_graph(self, input_a, input_b, gt_flow, edges=None):
         from .dist import allreduce_bucket_async, exchange_enabled, world_size
-        with_edges = self.hfem == "edges" and edges is not None
+        stage = self._pick_stage(edges, captured=True)
         if getattr(self, "_step_graphs", None) is None:
-            self._capture_step(with_edges)
-        if with_edges != (self._mining == "edges"):
-            raise ValueError("train_step: the captured step was built %s an edge map; this call is %s one"
-                             % (("without", "with") if with_edges else ("with", "without")))
-        if with_edges:
-            self.edges_in.copy_(self._edges_dev(edges).reshape(self.edges_in.shape), non_blocking=True)
-        if pairs is not None:  # the unsupervised step: frames into the slots, no ground truth
-            self._set_pairs(*pairs)
-        else:
-            self.gt.copy_(torch.as_tensor(gt_flow).to(dtype=torch.float32), non_blocking=True)
-            self.eng.set_inputs(input_a, input_b)
+            self._capture_step(stage)
+        self._set_inputs(input_a, input_b, gt_flow)
         world = world_size()
         self.step_count += 1
         if self._optim_entry:

@@ -105,7 +105,7 @@ def step_rows(args, dev):
         for k, fn in steps.items():
             times[k] += timed(fn, 1, args.steps)
     # the loss launches of the unsupervised step alone, on the trainer's own buffers, outside the graph
-    body = timed(lambda: uns._photometric_body(_hip.stream_ptr()), args.rounds, args.inner)
+    body = timed(lambda: uns._photo.launch(_hip.stream_ptr()), args.rounds, args.inner)
     rows = [row(k + " step (captured: %s)" % (getattr(tr, "_step_graphs", None) is not None), times[k])
             for k, tr in (("supervised", sup), ("unsupervised", uns))]
     rows.append(row("frames at five sizes + masks + loss_grad, as the step launches them", body))
