@@ -323,49 +323,13 @@ __device__ __forceinline__ void store_weight_copy4(const AdamTensor& t, long i, 
 __device__ __forceinline__ void store_weight_copy1(const AdamTensor& t, long i, float wi) {
   if (t.wx2 != nullptr) store_elem<x2_t>(t.wx2 + i, wi * t.scale);
 }
-__device__ __forceinline__ void adam_tensor(const AdamTensor& t, long cnt, float reg, float lr_t, float b1, float b2,
-                                            float eps, float gscale) {
-  auto one = [&](float wi, float gi, float& mi, float& vi) {
-    gi = gi * gscale + reg * wi;
-    mi = b1 * mi + (1.f - b1) * gi;
-    vi = b2 * vi + (1.f - b2) * gi * gi;
-    return wi - lr_t * mi / (sqrtf(vi) + eps);
-  };
-  const long n4 = cnt >> 2;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    float4 w = reinterpret_cast<float4*>(t.w)[i], m = reinterpret_cast<float4*>(t.m)[i], v = reinterpret_cast<float4*>(t.v)[i];
-    const float4 g = reinterpret_cast<const float4*>(t.g)[i];
-    w.x = one(w.x, g.x, m.x, v.x); w.y = one(w.y, g.y, m.y, v.y);
-    w.z = one(w.z, g.z, m.z, v.z); w.w = one(w.w, g.w, m.w, v.w);
-    reinterpret_cast<float4*>(t.m)[i] = m;
-    reinterpret_cast<float4*>(t.v)[i] = v;
-    reinterpret_cast<float4*>(t.w)[i] = w;
-    store_weight_copy4(t, i, w);
-  }
-  for (long i = 4 * n4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (long)gridDim.x * blockDim.x) {
-    float mi = t.m[i], vi = t.v[i];
-    const float wi = one(t.w[i], t.g[i], mi, vi);
-    t.m[i] = mi; t.v[i] = vi; t.w[i] = wi;
-    store_weight_copy1(t, i, wi);
-  }
-}
-__global__ void __launch_bounds__(256) adam_multi_kernel(const AdamTensor* __restrict__ tab, const long* __restrict__ n,
-                                                         const float* __restrict__ l2, float lr_t, float b1, float b2,
-                                                         float eps, float gscale) {
-  adam_tensor(tab[blockIdx.y], n[blockIdx.y], l2[blockIdx.y], lr_t, b1, b2, eps, gscale);
-}
 
-// The same with the per-step scalars read from device memory {lr_t, beta1, beta2, eps, grad_scale}: the launch
-// arguments no longer change from step to step, so the whole train step can be replayed as a hipGraph.
-__global__ void __launch_bounds__(256) adam_multi_dev_kernel(const AdamTensor* __restrict__ tab, const long* __restrict__ n,
-                                                             const float* __restrict__ l2, const float* __restrict__ hyper) {
-  adam_tensor(tab[blockIdx.y], n[blockIdx.y], l2[blockIdx.y], hyper[0], hyper[1], hyper[2], hyper[3], hyper[4]);
-}
-
-// The other optimisers of the reference's Net.train (net.py:1209-1288) and slim's per-tensor gradient clipping
-// (clip_gradient_norms = tf.clip_by_norm on each gradient, net.py:1381-1392), on the same table and grid as
-// adam_multi_dev_kernel.  hyper = {lr (lr_t for the Adam kinds), mu | beta1, beta2, eps, grad_scale, weight_decay,
-// clip_norm, 0}; G = grad_scale * g + reg * w is the gradient of the total loss, the quantity that is clipped.
+// The optimisers of the reference's Net.train (Adam, net.py:1290-1295; the others, net.py:1209-1288) and slim's
+// per-tensor gradient clipping (clip_gradient_norms = tf.clip_by_norm on each gradient, net.py:1381-1392), on the table
+// above and a dim3(FN2_OPTIM_PARTIALS, n_tensors) x 256 grid.  The per-step scalars are read from device memory, hyper =
+// {lr (lr_t for the Adam kinds), mu | beta1, beta2, eps, grad_scale, weight_decay, clip_norm, 0}: the launch arguments do
+// not change from step to step, so the whole train step can be replayed as a hipGraph.  G = grad_scale * g + reg * w is
+// the gradient of the total loss, the quantity that is clipped.
 //
 // Pass 1 (only when clipping): block (x, t) writes the sum of G^2 over the elements it strides to partials[t * 128 + x]:
 // a fixed per-thread order, a fixed shuffle tree, four wave sums added in order -- no atomics, every slot written.
@@ -1350,25 +1314,6 @@ int fn2_adam_step(float* w, float* m, float* v, const float* g, int64_t n, float
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, w, m, v, g, (long)n, lr_t,
                      beta1, beta2, eps, l2, grad_scale);
   FN2_CHECK_LAUNCH("adam");
-  return FN2_OK;
-}
-
-int fn2_adam_step_multi(const void* table, const int64_t* counts, const float* l2, int n_tensors, float lr, float beta1,
-                        float beta2, float eps, int step, float grad_scale, void* stream) {
-  FN2_REQUIRE(table && counts && l2 && n_tensors >= 1 && n_tensors <= 65535 && step >= 1, "adam_step_multi: bad arguments");
-  const float lr_t = adam_lr_t(lr, beta1, beta2, step);
-  hipLaunchKernelGGL(adam_multi_kernel, dim3(128, n_tensors), dim3(256), 0, (hipStream_t)stream,
-                     (const AdamTensor*)table, (const long*)counts, l2, lr_t, beta1, beta2, eps, grad_scale);
-  FN2_CHECK_LAUNCH("adam_multi");
-  return FN2_OK;
-}
-
-int fn2_adam_step_multi_dev(const void* table, const int64_t* counts, const float* l2, int n_tensors, const float* hyper,
-                            void* stream) {
-  FN2_REQUIRE(table && counts && l2 && hyper && n_tensors >= 1 && n_tensors <= 65535, "adam_step_multi_dev: bad arguments");
-  hipLaunchKernelGGL(adam_multi_dev_kernel, dim3(128, n_tensors), dim3(256), 0, (hipStream_t)stream,
-                     (const AdamTensor*)table, (const long*)counts, l2, hyper);
-  FN2_CHECK_LAUNCH("adam_multi_dev");
   return FN2_OK;
 }
 

@@ -8,7 +8,8 @@ Reference semantics (what tf.gradients + tf.train.AdamOptimizer compute for it):
             (weights .32 .08 .02 .01 .005, /5), + slim L2 regularisers (l2 = 4e-4 on slim.conv2d weights)
   optimiser Adam(lr from piecewise_constant LONG_SCHEDULE, beta 0.9/0.999, eps 1e-8), src/net.py:1205-1207,
             :1290-1295; src/training_schedules.py:46-53.  optimizer= 'sgd' | 'momentum' | 'adamw' and clip_grad_norm=
-            select the other optimisers of net.py:1209-1288 and slim's per-tensor clipping (fn2_optim_step_multi_dev)
+            select the other optimisers of net.py:1209-1288 and slim's per-tensor clipping; every kind, Adam included,
+            is one fn2_optim_step_multi_dev launch for all parameter tensors
   DP        not in the reference (single GPU).  Here: one process per GPU, each rank runs the step on its
             shard, ONE all-reduce of the flat gradient buffer, identical Adam on every rank.
 
@@ -212,8 +213,6 @@ class FlowNetSTrainer:
         self.l2_reg = float(weight_decay) if kind == "momentum" and weight_decay is not None else schedule["l2_regularization"]
         # slots per parameter: Adam's m and v, momentum's accumulator, none for sgd
         self.n_slots = {"sgd": 0, "momentum": 1, "adam": 2, "adamw": 2}[kind]
-        # the default optimiser without clipping keeps its own entry points (fn2_adam_step_multi / _dev) and launches
-        self._optim_entry = not (kind == "adam" and self.clip_norm == 0.0)
 
     def _gbuf(self, buf):
         """Gradient buffer mirroring an activation buffer (fp32, same shape)."""
@@ -348,6 +347,7 @@ class FlowNetSTrainer:
         eng._alloc_workspace()  # the input-gradient convolutions share the split-K scratch buffer
         self.refresh_backward_weights()
         self._plan_buckets(4)
+        self._build_optim_tables()
 
     def _head_forward_gemm(self, rec):
         """Forward of a flow head in the split-fp16 trainer as the engine's inference form (Engine._head_gemm): a 1x1
@@ -670,7 +670,7 @@ class FlowNetSTrainer:
                 _hip.check(self.lib.fn2_to_f16x2(_hip.ptr(wb), _hip.ptr(wsrc), _hip.ptr(gmap), wb.numel(), scale, s))
             else:
                 _hip.check(self.lib.fn2_gather_f32(_hip.ptr(wb), _hip.ptr(wsrc), _hip.ptr(gmap), wb.numel(), s))
-        if forward:  # (after an Adam step the forward copies are already fresh: fn2_adam_step_multi writes them)
+        if forward:  # (after an optimiser step the forward copies are fresh: fn2_optim_step_multi_dev writes them)
             for wx2, master, scale, frag_k in self.fwd_copies:
                 if frag_k:
                     _hip.check(self.lib.fn2_to_f16x2_frag(_hip.ptr(wx2), _hip.ptr(master), None, master.numel(), scale, frag_k, s))
@@ -794,24 +794,13 @@ class FlowNetSTrainer:
         return float(sum(0.5 * l2 * float((p["w"].double() ** 2).sum()) for p in self.params if p["reg"]))
 
     def apply_gradients(self, reduced_world=None):
-        """All-reduce (unless the caller already did: reduced_world = number of ranks summed) + Adam."""
+        """All-reduce (unless the caller already did: reduced_world = number of ranks summed) + the optimiser update."""
         from .dist import allreduce_gradients
-        # RCCL sum over xGMI; the mean is folded into Adam's grad_scale
+        # RCCL sum over xGMI; the mean is folded into the update's grad_scale
         world = reduced_world if reduced_world is not None else allreduce_gradients(self.grad_arena)
         self.step_count += 1
-        if self._optim_entry:
-            self._upload_optim_hyper(world)
-            self._launch_optim(_hip.stream_ptr())
-            self.refresh_backward_weights(forward=False)
-            return
-        lr = self.learning_rate(self.step_count - 1)
-        b1, b2 = self.schedule["momentum"], self.schedule["momentum2"]
-        s = _hip.stream_ptr()
-        if getattr(self, "_adam_table", None) is None:  # one launch for all parameter tensors
-            self._build_adam_tables()
-        _hip.check(self.lib.fn2_adam_step_multi(_hip.ptr(self._adam_table), _hip.ptr(self._adam_counts),
-                                                _hip.ptr(self._adam_l2), len(self.params), lr, b1, b2, self.eps,
-                                                self.step_count, 1.0 / (world * self.loss_scale), s))
+        self._upload_optim_hyper(world)
+        self._launch_optim(_hip.stream_ptr())
         self.refresh_backward_weights(forward=False)
 
     # ------------------------------------------------------------------ validation
@@ -879,34 +868,42 @@ class FlowNetSTrainer:
             lr = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
         return [lr, b1, b2, self.eps, 1.0 / (world * self.loss_scale), self.weight_decay, self.clip_norm, 0.0]
 
-    def _alloc_optim_buffers(self):
-        """The eight per-step floats (device + pinned staging) and, when clipping, the per-block partial sums; allocated
-        once, outside any capture."""
-        if getattr(self, "_ohyper", None) is not None:
-            return
-        self._ohyper = torch.zeros(8, dtype=torch.float32, device=self.dev)
-        self._ohyper_host = torch.zeros(8, dtype=torch.float32).pin_memory()
-        self._ohyper_done = None
+    def _build_optim_tables(self):
+        """What fn2_optim_step_multi_dev reads, built once at construction (nothing is allocated in a capture): the table
+        {w, m, v, g, split-fp16 forward copy of w (or 0), its scale} per parameter tensor -- the update rewrites the copy the
+        forward convolutions read while it has the new master in registers --, the counts and L2 coefficients, the eight
+        per-step floats (device + pinned staging) and, when clipping, the per-block partial sums."""
+        l2 = self.l2_reg
+        fwd = {master.data_ptr(): (wx2.data_ptr(), scale, frag_k) for wx2, master, scale, frag_k in self.fwd_copies}
+        ptrs = []
+        for p in self.params:
+            wx2, scale, frag_k = fwd.get(p["w"].data_ptr(), (0, 1.0, 0))
+            bits = int(np.float32(scale).view(np.uint32)) | (int(frag_k) << 32)
+            slot = lambda t: t.data_ptr() if t is not None else 0  # (a slot this optimiser lacks: null, never read)
+            ptrs.append([p["w"].data_ptr(), slot(p["m"]), slot(p["v"]), p["g"].data_ptr(), wx2, bits])
+        self._adam_table = torch.tensor(ptrs, dtype=torch.int64, device=self.dev)
+        self._adam_counts = torch.tensor([p["n"] for p in self.params], dtype=torch.int64, device=self.dev)
+        self._adam_l2 = torch.tensor([l2 if p["reg"] else 0.0 for p in self.params], dtype=torch.float32, device=self.dev)
+        self._hyper = torch.zeros(8, dtype=torch.float32, device=self.dev)
+        self._hyper_host = torch.zeros(8, dtype=torch.float32).pin_memory()
+        self._hyper_event = None
         if self.clip_norm > 0.0:  # (every slot is written by the first pass: no zeroing)
             self._partials = torch.empty(len(self.params) * _hip.OPTIM_PARTIALS, dtype=torch.float32, device=self.dev)
 
     def _upload_optim_hyper(self, world):
-        """Pinned staging as the captured Adam step's: the previous step's copy has been consumed once its update ran
-        (same stream order); the event makes the host wait for exactly that before overwriting the eight floats."""
-        self._alloc_optim_buffers()
-        if self._ohyper_done is not None:
-            self._ohyper_done.synchronize()
-        self._ohyper_host.copy_(torch.tensor(self._optim_hyper(world), dtype=torch.float32))
-        self._ohyper.copy_(self._ohyper_host, non_blocking=True)
-        self._ohyper_done = torch.cuda.Event()
-        self._ohyper_done.record()
+        """The step's eight floats through pinned staging: the device copy is overwritten in stream order, behind the
+        previous step's update; the event makes the host wait until the previous copy has left the pinned floats."""
+        if self._hyper_event is not None:
+            self._hyper_event.synchronize()
+        self._hyper_host.copy_(torch.tensor(self._optim_hyper(world), dtype=torch.float32))
+        self._hyper.copy_(self._hyper_host, non_blocking=True)
+        self._hyper_event = torch.cuda.Event()
+        self._hyper_event.record()
 
     def _launch_optim(self, s):
         """The per-tensor squared norms (only when clipping) and the update: two launches for all parameter tensors."""
-        if getattr(self, "_adam_table", None) is None:
-            self._build_adam_tables()
         args = (_hip.ptr(self._adam_table), _hip.ptr(self._adam_counts), _hip.ptr(self._adam_l2), len(self.params),
-                _hip.ptr(self._ohyper))
+                _hip.ptr(self._hyper))
         partials = None
         if self.clip_norm > 0.0:
             partials = _hip.ptr(self._partials)
@@ -953,7 +950,7 @@ class FlowNetSTrainer:
     def train_step(self, input_a, input_b, gt_flow, edges=None):
         """One step: forward, loss, backward, gradient all-reduce (data parallel), Adam.  The launch sequence is
         captured once as hipGraph segments (cut where a gradient bucket is handed to the all-reduce) and replayed:
-        the per-step scalars of Adam live in device memory, so nothing in the segments changes between steps.  The
+        the per-step scalars of the update live in device memory, so nothing in the segments changes between steps.  The
         mining losses are part of the graph: their pixel weights come from fn2_hfem_hard_weights (one launch for the
         five scales) or fn2_hfem_edge_weights, on buffers allocated before the capture.
         edges: the edge map of the 'edges' mode, [N,H,W] or [N,H,W,1]; the other modes ignore it.  Whether it is given
@@ -1032,8 +1029,8 @@ class FlowNetSTrainer:
     # ------------------------------------------------------------------ captured step
     def _segment_body(self, seg):
         """Launches of segment `seg` on torch's current stream.  Segment 0 starts with the zeroing, the forward and
-        the loss; segment i ends behind the backward launch that completes gradient bucket i; the last segment is Adam
-        and the refresh of the derived weight copies."""
+        the loss; segment i ends behind the backward launch that completes gradient bucket i; the last segment is the
+        optimiser update and the refresh of the derived weight copies."""
         eng, s = self.eng, _hip.stream_ptr()
         nseg = len(self._seg_ends)
         if seg == 0:
@@ -1048,41 +1045,14 @@ class FlowNetSTrainer:
                 for fn, args in ops:
                     _hip.check(fn(*args, s))
             return
-        if self._optim_entry:
-            self._launch_optim(s)
-            self.refresh_backward_weights(forward=False)
-            return
-        if getattr(self, "_adam_table", None) is None:
-            self._build_adam_tables()
-        _hip.check(self.lib.fn2_adam_step_multi_dev(_hip.ptr(self._adam_table), _hip.ptr(self._adam_counts),
-                                                    _hip.ptr(self._adam_l2), len(self.params), _hip.ptr(self._hyper), s))
+        self._launch_optim(s)
         self.refresh_backward_weights(forward=False)
-
-    def _build_adam_tables(self):
-        """{w, m, v, g, split-fp16 forward copy of w (or 0), its scale} per parameter tensor (fn2_adam_step_multi): Adam
-        rewrites the copy the forward convolutions read while it has the new master in registers."""
-        l2 = self.l2_reg
-        fwd = {master.data_ptr(): (wx2.data_ptr(), scale, frag_k) for wx2, master, scale, frag_k in self.fwd_copies}
-        ptrs = []
-        for p in self.params:
-            wx2, scale, frag_k = fwd.get(p["w"].data_ptr(), (0, 1.0, 0))
-            bits = int(np.float32(scale).view(np.uint32)) | (int(frag_k) << 32)
-            slot = lambda t: t.data_ptr() if t is not None else 0  # (a slot this optimiser lacks: null, never read)
-            ptrs.append([p["w"].data_ptr(), slot(p["m"]), slot(p["v"]), p["g"].data_ptr(), wx2, bits])
-        self._adam_table = torch.tensor(ptrs, dtype=torch.int64, device=self.dev)
-        self._adam_counts = torch.tensor([p["n"] for p in self.params], dtype=torch.int64, device=self.dev)
-        self._adam_l2 = torch.tensor([l2 if p["reg"] else 0.0 for p in self.params], dtype=torch.float32, device=self.dev)
 
     def _capture_step(self, stage):
         from .dist import exchange_enabled
         # one segment per gradient bucket when the gradients are exchanged, else a single backward segment
         self._seg_ends = [i for i, _ in self.buckets] if exchange_enabled() else [len(self.bwd_ops) - 1]
         self._captured = stage  # (allocated, and with it the _gbufs of the predictions: nothing is allocated in the capture)
-        self._hyper = torch.zeros(5, dtype=torch.float32, device=self.dev)
-        self._hyper_host = torch.zeros(5, dtype=torch.float32).pin_memory()
-        self._build_adam_tables()
-        if self._optim_entry:
-            self._alloc_optim_buffers()
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream())
         graphs = []
@@ -1110,21 +1080,7 @@ class FlowNetSTrainer:
         self._set_inputs(input_a, input_b, gt_flow)
         world = world_size()
         self.step_count += 1
-        if self._optim_entry:
-            self._upload_optim_hyper(world)
-        else:
-            lr = self.learning_rate(self.step_count - 1)
-            b1, b2 = self.schedule["momentum"], self.schedule["momentum2"]
-            t = float(self.step_count)
-            lr_t = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
-            # pinned staging: the previous step's copy has been consumed once its Adam segment ran (same stream order);
-            # the event makes the host wait for exactly that before overwriting the five floats
-            if getattr(self, "_hyper_done", None) is not None:
-                self._hyper_done.synchronize()
-            self._hyper_host.copy_(torch.tensor([lr_t, b1, b2, self.eps, 1.0 / (world * self.loss_scale)], dtype=torch.float32))
-            self._hyper.copy_(self._hyper_host, non_blocking=True)
-            self._hyper_done = torch.cuda.Event()
-            self._hyper_done.record()
+        self._upload_optim_hyper(world)
         s = _hip.stream_ptr()
         pending = []
         for i in range(len(self._seg_ends)):

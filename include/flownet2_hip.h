@@ -437,33 +437,27 @@ int fn2_gather_f32(float* dst, const float* src, const int32_t* map, int64_t n, 
 /* tf.train.AdamOptimizer update of n parameters with g' = grad_scale*g + l2*w (slim l2_regularizer). */
 int fn2_adam_step(float* w, float* m, float* v, const float* g, int64_t n, float lr, float beta1, float beta2,
                   float eps, int step, float l2, float grad_scale, void* stream);
-/* The same update (tf.train.AdamOptimizer.apply_gradients, net.py:1290-1295) for n_tensors parameter tensors in
- * ONE launch.  table: device array of six 64-bit words per tensor: {float* w, float* m, float* v, const float* g,
- * void* w_f16x2, float scale (low 32 bits) | int frag_k (high 32 bits: 0 = row-major copy, else the packed row length k of a
- * wgt_layout-2 copy)} -- w_f16x2: the split-fp16 copy of w the convolutions read (same packed
- * geometry), rewritten as w * scale by the same pass, or NULL; every pointer 16-byte aligned.  counts / l2: device
- * arrays of element counts (int64) and L2 coefficients (0 where the reference does not regularise). */
-int fn2_adam_step_multi(const void* table, const int64_t* counts, const float* l2, int n_tensors, float lr, float beta1,
-                        float beta2, float eps, int step, float grad_scale, void* stream);
-/* fn2_adam_step_multi with the per-step scalars in device memory: hyper = {lr_t, beta1, beta2, eps, grad_scale} with
- * lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) (tf.train.AdamOptimizer's form, net.py:1290-1295).  The launch
- * arguments are then the same every step, which lets the train step be captured once and replayed as a hipGraph. */
-int fn2_adam_step_multi_dev(const void* table, const int64_t* counts, const float* l2, int n_tensors, const float* hyper,
-                            void* stream);
-/* The other optimisers Net.train selects from train_params_dict['optimizer'] (net.py:1209-1288) and the per-tensor
- * gradient clipping it hands to slim.learning.create_train_op (clip_gradient_norm, net.py:1381-1392: tf.clip_by_norm on
- * each gradient, not a global norm), on the table / counts / l2 arrays of fn2_adam_step_multi_dev.
+/* fn2_optim_step_multi_dev and its clipping pass fn2_optim_grad_sumsq_multi: the optimisers Net.train selects from
+ * train_params_dict['optimizer'] (net.py:1209-1295) and the per-tensor gradient clipping it hands to
+ * slim.learning.create_train_op (clip_gradient_norm, net.py:1381-1392: tf.clip_by_norm on each gradient, not a global
+ * norm), for n_tensors parameter tensors in ONE launch each.
+ * table: device array of six 64-bit words per tensor: {float* w, float* m, float* v, const float* g, void* w_f16x2,
+ * float scale (low 32 bits) | int frag_k (high 32 bits: 0 = row-major copy, else the packed row length k of a wgt_layout-2
+ * copy)} -- w_f16x2: the split-fp16 copy of w the convolutions read (same packed geometry), rewritten as w * scale by
+ * the pass that updates w (every kind), or NULL; every pointer 16-byte aligned.  counts / l2: device arrays of element
+ * counts (int64) and L2 coefficients (0 where the reference does not regularise).
+ * hyper: eight floats in device memory {lr (lr_t for the Adam kinds), mu or beta1, beta2, eps, grad_scale, weight_decay,
+ * clip_norm, 0}: the launch arguments are the same every step, which lets the train step be captured once and replayed
+ * as a hipGraph.
  *   G = grad_scale * g + l2 * w      the gradient of the total loss (the regulariser is part of it): what is clipped
  *   clipping (clip_norm > 0)         S = sum G^2 over the tensor, G <- G * clip_norm / max(sqrt(S), clip_norm)
  *   FN2_OPTIM_SGD       tf.train.GradientDescentOptimizer:  w' = w - lr G                      (no slots, words 1-2 unread)
  *   FN2_OPTIM_MOMENTUM  tf.train.MomentumOptimizer(lr, mu, use_nesterov=True), TF's ApplyMomentum:
  *                       a' = mu a + G,  w' = w - (lr G + lr mu a')                             (slot 0 = a, <var>/Momentum)
- *   FN2_OPTIM_ADAM      fn2_adam_step_multi_dev's update on the (clipped) G
+ *   FN2_OPTIM_ADAM      tf.train.AdamOptimizer (net.py:1290-1295), lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t):
+ *                       m' = beta1 m + (1 - beta1) G,  v' = beta2 v + (1 - beta2) G^2,  w' = w - lr_t m' / (sqrt(v') + eps)
  *   FN2_OPTIM_ADAMW     tf.contrib.opt.extend_with_decoupled_weight_decay(AdamOptimizer): w_d = w - weight_decay * w (not
- *                       scaled by the rate, every tensor), G taken at the undecayed w, Adam's update applied to w_d
- * hyper: eight floats in device memory {lr (lr_t for the Adam kinds), mu or beta1, beta2, eps, grad_scale, weight_decay,
- * clip_norm, 0}, so both launches can be captured and replayed.  Every kind rewrites the split-fp16 copy of w as
- * fn2_adam_step_multi does. */
+ *                       scaled by the rate, every tensor), G taken at the undecayed w, Adam's update applied to w_d */
 enum fn2_optim_kind { FN2_OPTIM_SGD = 0, FN2_OPTIM_MOMENTUM = 1, FN2_OPTIM_ADAM = 2, FN2_OPTIM_ADAMW = 3 };
 #define FN2_OPTIM_PARTIALS 128 /* floats of `partials` per tensor */
 /* Clipping, pass 1: partials[t * FN2_OPTIM_PARTIALS + x] = the sum of G^2 over the elements block x of tensor t strides

@@ -354,20 +354,6 @@ def test_adamw_without_decay_is_the_adam_kind_bit_for_bit(clip):
     assert not np.array_equal(fa.view(np.uint32), a.farena.view(np.uint32))
 
 
-@pytest.mark.gpu
-def test_adam_kind_without_clipping_is_the_adam_entry_bit_for_bit():
-    from src import _hip
-    lib = _hip.lib()
-    a, b = Run(800, "adam"), Run(800, "adam")
-    hyper = hyper_of("adam", step=7)
-    fa, xa, _ = a.step("adam", hyper, False)
-    table, hd = b.table("adam"), dev(hyper[:5].copy())
-    _hip.check(lib.fn2_adam_step_multi_dev(_hip.ptr(table), _hip.ptr(b.counts), _hip.ptr(b.l2s), len(ops.ADAM_TENSORS),
-                                           _hip.ptr(hd), _hip.stream_ptr()))
-    np.testing.assert_array_equal(fa.view(np.uint32), host(b.fd).view(np.uint32))
-    np.testing.assert_array_equal(xa.view(np.uint32), host(b.xd).view(np.uint32))
-
-
 # ------------------------------------------------------------------------------------------------ trainer level
 def batch(n, seed):
     from test_gpu_train import data
@@ -409,10 +395,11 @@ def check_update(pool, kind, name, b, a, hyper, reg):
 def trainer_hyper(tr, step):
     """The eight floats of global step `step` (0-based), computed here from the schedule functions."""
     from src.training_schedules import learning_rate, momentum_value
-    lr = learning_rate(tr.schedule, step, tr.train_params)
+    params = getattr(tr, "train_params", None)           # (set by the command lines and by tests, not by the trainer)
+    lr = learning_rate(tr.schedule, step, params)
     mu, b2 = tr.schedule["momentum"], tr.schedule["momentum2"]
     if tr.optimizer == "momentum":
-        mu = momentum_value(tr.schedule, step, tr.train_params, tr.momentum, tr.min_momentum, tr.max_momentum)
+        mu = momentum_value(tr.schedule, step, params, tr.momentum, tr.min_momentum, tr.max_momentum)
     if tr.optimizer in ("adam", "adamw"):
         t = float(step + 1)
         lr = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - mu ** t)
@@ -529,31 +516,59 @@ def test_momentum_checkpoint_round_trip(fmt, tmp_path):
 
 
 @pytest.mark.gpu
-def test_default_trainer_never_calls_the_new_entries(monkeypatch):
-    """optimizer='adam' without clipping keeps fn2_adam_step_multi / fn2_adam_step_multi_dev: eager and captured steps run
-    with the new entries replaced by functions that raise (test_adam_steps_match_oracle checks the values)."""
+def test_default_trainer_is_the_adam_kind_on_the_one_update_path(monkeypatch):
+    """optimizer='adam' without clipping is a kind like the others: the eager and the captured step launch
+    fn2_optim_step_multi_dev with the Adam kind and null partials, and upload the same eight floats.  The two optimiser
+    entries of trainer.lib are wrapped by functions that note the call and pass it on
+    (test_adam_steps_match_oracle checks the values)."""
     from src import weights as W
     from src.trainer import FlowNetSTrainer
     tr = FlowNetSTrainer(W.init_weights("FlowNetS", 6), 1, 128, 128, dtype="f16x2")
+    calls = []
 
-    def forbidden(*a):
-        raise AssertionError("the default trainer launched an optimiser entry other than Adam's")
-    monkeypatch.setattr(tr.lib, "fn2_optim_grad_sumsq_multi", forbidden)
-    monkeypatch.setattr(tr.lib, "fn2_optim_step_multi_dev", forbidden)
+    def record(name):
+        real = getattr(tr.lib, name)
+
+        def call(*args):
+            calls.append((name, args))
+            return real(*args)
+        monkeypatch.setattr(tr.lib, name, call)
+    record("fn2_optim_grad_sumsq_multi")
+    record("fn2_optim_step_multi_dev")
+
+    def taken():
+        out = calls[:]
+        del calls[:]
+        return out
+
+    def device_hyper(t):
+        return t._hyper.cpu().numpy().view(np.uint32)
     assert tr.optimizer == "adam" and tr.clip_norm == 0.0 and tr.m_arena is not None and tr.v_arena is not None
     tr.forward_backward(*batch(1, 2))
+    assert taken() == []
     tr.apply_gradients()
+    (name, args), = taken()                                         # exactly one launch, and no squared norms
+    assert name == "fn2_optim_step_multi_dev" and args[0] == KIND_CODE["adam"] and args[6] is None
+    np.testing.assert_array_equal(device_hyper(tr), trainer_hyper(tr, 0).view(np.uint32))
     tr.train_step(*batch(1, 3))
+    (name, args), = taken()                                         # the capture; nothing is launched un-captured
+    assert name == "fn2_optim_step_multi_dev" and args[0] == KIND_CODE["adam"] and args[6] is None
+    np.testing.assert_array_equal(device_hyper(tr), trainer_hyper(tr, 1).view(np.uint32))
     tr.train_step(*batch(1, 4))
-    assert tr.step_count == 3 and tr._step_graphs is not None and getattr(tr, "_ohyper", None) is None
+    assert taken() == []                                            # a replay calls no entry
+    np.testing.assert_array_equal(device_hyper(tr), trainer_hyper(tr, 2).view(np.uint32))
+    assert tr.step_count == 3 and tr._step_graphs is not None
     assert sorted(k.rsplit("/", 1)[1] for k in tr.optimizer_state() if "/weights/" in k)[0] == "Adam"
     # a checkpoint of the Momentum optimiser holds no slot of Adam's: the step counter alone is restored
     foreign = {"FlowNetS/conv1/weights/Momentum": np.zeros(1, np.float32), "global_step": np.int64(5)}
     assert tr.load_optimizer_state(foreign) == 0 and tr.step_count == 5
     clipped = FlowNetSTrainer(W.init_weights("FlowNetS", 6), 1, 128, 128, dtype="f16x2", clip_grad_norm=1.0)
-    with pytest.raises(AssertionError, match="other than Adam"):
-        clipped.forward_backward(*batch(1, 2))
-        clipped.apply_gradients()
+    clipped.forward_backward(*batch(1, 2))
+    clipped.apply_gradients()
+    (sumsq, sargs), (step, args) = taken()                          # both passes, in that order, on the same partials
+    assert sumsq == "fn2_optim_grad_sumsq_multi" and step == "fn2_optim_step_multi_dev" and args[0] == KIND_CODE["adam"]
+    assert args[6] is not None and args[6].value and args[6].value == sargs[5].value == clipped._partials.data_ptr()
+    np.testing.assert_array_equal(device_hyper(clipped), trainer_hyper(clipped, 0).view(np.uint32))
 
 
 @pytest.mark.gpu

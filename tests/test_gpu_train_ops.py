@@ -574,8 +574,7 @@ def adam_arena(seed):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("step", [1, 7])
-@pytest.mark.parametrize("entry", ["fn2_adam_step_multi", "fn2_adam_step_multi_dev"])
-def test_adam_step_multi_and_its_weight_copies(entry, step):
+def test_adam_step_multi_and_its_weight_copies(step):
     from src import _hip
     lib = _hip.lib()
     import torch
@@ -585,21 +584,16 @@ def test_adam_step_multi_and_its_weight_copies(entry, step):
     rows = []
     for (n, l2, copy, scale, frag_k), o in zip(ADAM_TENSORS, offs):
         wx2 = xd.data_ptr() + 4 * o["x"] if copy is not None else 0
-        bits = int(np.float32(scale).view(np.uint32)) | (int(frag_k) << 32)     # as Trainer._build_adam_tables
+        bits = int(np.float32(scale).view(np.uint32)) | (int(frag_k) << 32)     # as Trainer._build_optim_tables
         rows.append([fd.data_ptr() + 4 * o[k] for k in "wmvg"] + [wx2, bits])
         assert all(p % 16 == 0 for p in rows[-1][:5])
     table = torch.tensor(rows, dtype=torch.int64, device="cuda")
     counts = torch.tensor([t[0] for t in ADAM_TENSORS], dtype=torch.int64, device="cuda")
     l2s = torch.tensor([t[1] for t in ADAM_TENSORS], dtype=torch.float32, device="cuda")
     lr_t = adam_lr_t(LR, B1, B2, step)
-    if entry == "fn2_adam_step_multi":
-        rc = lib.fn2_adam_step_multi(_hip.ptr(table), _hip.ptr(counts), _hip.ptr(l2s), len(rows), LR, B1, B2, EPS, step,
-                                     GSCALE, _hip.stream_ptr())
-    else:
-        hyper = dev(np.array([lr_t, B1, B2, EPS, GSCALE], np.float32))
-        rc = lib.fn2_adam_step_multi_dev(_hip.ptr(table), _hip.ptr(counts), _hip.ptr(l2s), len(rows), _hip.ptr(hyper),
-                                         _hip.stream_ptr())
-    _hip.check(rc)
+    hyper = dev(np.array([lr_t, B1, B2, EPS, GSCALE, 0.0, 0.0, 0.0], np.float32))
+    _hip.check(lib.fn2_optim_step_multi_dev(_hip.OPTIM_KINDS["adam"], _hip.ptr(table), _hip.ptr(counts), _hip.ptr(l2s), len(rows),
+                                            _hip.ptr(hyper), None, _hip.stream_ptr()))
     fgot, xgot = host(fd), host(xd)
     touched_f, touched_x = np.zeros(farena.size, bool), np.zeros(xarena.size, bool)
     for (n, l2, copy, scale, frag_k), o in zip(ADAM_TENSORS, offs):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Step time of the captured FlowNetS train step (batch 8, 384x512, split fp16: the trainer of bench.py --mode train) for
-every optimiser, with and without per-tensor gradient clipping, against the Adam step of the same build -- whose launch
-sequence is the one the trainer had before the other optimisers existed.  One process; every variant is captured and
+every optimiser, with and without per-tensor gradient clipping, against the Adam step of the same build -- the default
+trainer, the step bench.py --mode train measures.  One process; every variant is captured and
 warmed first, then the variants are timed in alternating rounds (device events around `--steps` replays each) and the
 median round is reported, with the spread.  A record, not a threshold.  One JSON line on stdout.
 
