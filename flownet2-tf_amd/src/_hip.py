@@ -57,6 +57,12 @@ class Fn2PhotometricLevel(C.Structure):
                 ("dpred", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("scale", C.c_float), ("weight", C.c_float)]
 
 
+class Fn2CensusLevel(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("img", C.c_void_p), ("mask", C.c_void_p), ("dpred", C.c_void_p),
+                ("grey", C.c_void_p), ("warp", C.c_void_p), ("valid", C.c_void_p), ("coef", C.c_void_p),
+                ("count", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("scale", C.c_float), ("weight", C.c_float)]
+
+
 class Fn2SparseEpeLevel(C.Structure):
     _fields_ = [("pred", C.c_void_p), ("label", C.c_void_p), ("dpred", C.c_void_p), ("count", C.c_void_p),
                 ("h", C.c_int32), ("w", C.c_int32), ("weight", C.c_float)]
@@ -122,6 +128,9 @@ PROTOTYPES = {
     "fn2_photometric_masks": (_i, [C.POINTER(Fn2PhotometricLevel), _i, _i, _f, _f, _p]),
     "fn2_photometric_loss_grad": (_i, [C.POINTER(Fn2PhotometricLevel), _i, _i, _f, _f, _p, _p]),
     "fn2_smoothness_loss_grad": (_i, [C.POINTER(Fn2PhotometricLevel), _i, _i, _i, _f, _f, _f, _f, _i, _p, _p]),
+    "fn2_census_warp": (_i, [C.POINTER(Fn2CensusLevel), _i, _i, _p]),
+    "fn2_census_cost": (_i, [C.POINTER(Fn2CensusLevel), _i, _i, _f, _p, _p]),
+    "fn2_census_grad": (_i, [C.POINTER(Fn2CensusLevel), _i, _i, _f, _p]),
     "fn2_sparse_epe_count": (_i, [C.POINTER(Fn2SparseEpeLevel), _i, _i, _p]),
     "fn2_sparse_epe_loss_grad": (_i, [C.POINTER(Fn2SparseEpeLevel), _i, _i, _f, _p, _p]),
     "fn2_leaky_bwd": (_i, [_tp, _tp, _p, _p]),

@@ -2,7 +2,8 @@
                                  --ckpt-format npz|tf --training_schedule one_cycle --optimizer sgd|momentum|adamw
                                  --momentum M | --min_momentum A --max_momentum B --weight_decay D --clip_grad_norm C
                                  --unsupervised --no-augment|--augmentation pair --photometric_q Q --occ_alpha A
-                                 --occ_beta B --smoothness_weight S --smoothness_order 1|2 --edge_lambda L
+                                 --occ_beta B --data_term photometric|census --smoothness_weight S
+                                 --smoothness_order 1|2 --edge_lambda L
                                  --sparse_gt --crop]
 The reference's src/flownet_s/train.py:8-40 + Net.train (net.py:1002-1400) over the HIP trainer: FlyingChairs-style
 augmentation on the GPU, multiscale EPE loss, Adam on LONG_SCHEDULE (or the optimiser and schedule named), periodic
@@ -11,6 +12,7 @@ reference's TFRecords are built from exactly these).  Under torch.distributed.ru
 the gradients are all-reduced (data parallel).
 --unsupervised: no ground truth is read (`image_a image_b` lines are accepted); every pair runs in both directions, so
 --batch is even and batch / 2 pairs go in per step; the loss is the occlusion-aware photometric loss (src/photometric.py),
+or with --data_term census the ternary census term (src/census.py) on every scale that holds a 7 x 7 patch,
 with --smoothness_weight > 0 plus the edge-aware smoothness term (src/smoothness.py).  The one augmentation that keeps
 brightness constancy is --augmentation pair (flips, channel permutation and ONE colour record for both frames, no crop).
 --sparse_gt: the third field of a line is a KITTI flow .png (or a .flo with unknown pixels); pixels without ground truth take
@@ -129,6 +131,9 @@ def add_unsupervised_arguments(ap):
                          "accepted, --batch is even (batch / 2 pairs per step, both directions); needs --no-augment or "
                          "--augmentation pair")
     ap.add_argument("--photometric_q", type=float, default=0.4, help="exponent of the robust loss (|d| + 0.01)^q")
+    ap.add_argument("--data_term", default="photometric", choices=["photometric", "census"],
+                    help="data term of --unsupervised: photometric (default: raw brightness differences) or census (the "
+                         "ternary census transform, for pairs whose exposure changes between the frames; src/census.py)")
     ap.add_argument("--occ_alpha", type=float, default=0.01, help="forward-backward test: factor on the squared magnitudes")
     ap.add_argument("--occ_beta", type=float, default=0.5, help="forward-backward test: constant, in pixels^2 of the level")
     ap.add_argument("--smoothness_weight", type=float, default=0.0,
@@ -140,7 +145,11 @@ def add_unsupervised_arguments(ap):
 
 def unsupervised_kwargs(flags):
     """The trainer's unsupervised arguments from parsed flags, checked before anything touches a device."""
+    from ..census import check_data_term
+    data_term = check_data_term(getattr(flags, "data_term", "photometric"), True)
     if not getattr(flags, "unsupervised", False):
+        if data_term != "photometric":
+            raise ValueError("--data_term %s is a term of the unsupervised loss: it needs --unsupervised" % data_term)
         return {}
     if getattr(flags, "augment", True) and getattr(flags, "augmentation", "plugin") != "pair":
         raise ValueError("--unsupervised needs --no-augment: both augmentations recolour the two frames independently, "
@@ -150,6 +159,8 @@ def unsupervised_kwargs(flags):
     from ..photometric import check_constants
     alpha, beta, q = check_constants(flags.occ_alpha, flags.occ_beta, flags.photometric_q)
     kwargs = dict(unsupervised=True, photometric_q=q, occ_alpha=alpha, occ_beta=beta)
+    if data_term != "photometric":  # (the default: nothing handed on)
+        kwargs.update(data_term=data_term)
     from ..smoothness import check_constants as check_smoothness
     order, edge_lambda, _, weight = check_smoothness(getattr(flags, "smoothness_order", 1), getattr(flags, "edge_lambda", 150.0),
                                                      1e-3, getattr(flags, "smoothness_weight", 0.0))

@@ -8,7 +8,7 @@ same stage.launch(stream), so they issue one launch sequence.
   zeroed    the device buffers of the stage that the step's zeroing has to clear as well (counters)"""
 import torch
 
-from . import _hip, losses, photometric, sparse_epe
+from . import _hip, census, losses, photometric, sparse_epe
 
 
 class _Stage:
@@ -127,8 +127,8 @@ class Photometric(_Stage):
         self.table = photometric.level_table(table)
         self.zeroed = [self.counts]
 
-    def launch(self, s):
-        tr, lib, nl = self.tr, self.tr.lib, len(self.levels)
+    def _frames_and_masks(self, s):
+        tr, lib = self.tr, self.tr.lib
         for img in self.imgs.values():
             if min(img.shape[1:3]) == 1:
                 # no pixel of a 1-high or 1-wide level is valid (0 <= Y < h - 1 is empty), so its frames are never read;
@@ -136,13 +136,66 @@ class Photometric(_Stage):
                 continue
             _hip.check(lib.fn2_downsample_f32(_hip.ptr(tr.eng.in_a), _hip.ptr(img), tr.N, tr.H, tr.W, 3, int(img.shape[1]),
                                               int(img.shape[2]), s))
-        _hip.check(lib.fn2_photometric_masks(self.table, nl, tr.N, tr.occ_alpha, tr.occ_beta, s))
-        _hip.check(lib.fn2_photometric_loss_grad(self.table, nl, tr.N, tr.photometric_q, tr.loss_scale,
-                                                 _hip.ptr(tr.loss_dev), s))
-        if tr.smoothness_weight > 0.0:  # one more launch over the same table
-            _hip.check(lib.fn2_smoothness_loss_grad(self.table, nl, tr.N, tr.smoothness_order, tr.edge_lambda,
-                                                    tr.smoothness_eps, tr.smoothness_weight, tr.loss_scale, 1,
+        _hip.check(lib.fn2_photometric_masks(self.table, len(self.levels), tr.N, tr.occ_alpha, tr.occ_beta, s))
+
+    def _photometric(self, table, s):
+        tr = self.tr
+        _hip.check(tr.lib.fn2_photometric_loss_grad(table, len(table), tr.N, tr.photometric_q, tr.loss_scale,
                                                     _hip.ptr(tr.loss_dev), s))
+
+    def _smoothness(self, s):
+        tr = self.tr
+        if tr.smoothness_weight > 0.0:  # one more launch over the same table
+            _hip.check(tr.lib.fn2_smoothness_loss_grad(self.table, len(self.levels), tr.N, tr.smoothness_order,
+                                                       tr.edge_lambda, tr.smoothness_eps, tr.smoothness_weight,
+                                                       tr.loss_scale, 1, _hip.ptr(tr.loss_dev), s))
+
+    def launch(self, s):
+        self._frames_and_masks(s)
+        self._photometric(self.table, s)
+        self._smoothness(s)
+
+
+class Census(Photometric):
+    """data_term='census': the frames, masks and scales of Photometric, and on every scale that holds a 7 x 7 patch the
+    ternary census term of src/census.py in its place -- G, the planes W / DX / DY, V, the planes S / c and one count Mc
+    per such scale.  The scales below 7 pixels (the 6 x 8 predict_flow6 of a 384 x 512 frame) have no interior pixel and
+    would train on nothing but the paths through their upsampling: they keep the photometric term, on a table of their
+    own.  launch: the frames, the masks of all scales, the three census launches, the photometric launch on the small
+    scales if there is one, then the smoothness term over all scales as in Photometric."""
+    kind = "census"
+
+    def _alloc(self, levels):
+        super()._alloc(levels)
+        self.grey, self.warp, self.valid, self.coef, big, small = {}, {}, {}, {}, [], []
+        names = [p for p, pred, _g, _wgt in levels if min(pred.shape[1:3]) >= census.PATCH]
+        self.census_counts = self._new(max(len(names), 1))
+        for i, (p, pred, g, wgt) in enumerate(levels):
+            n, h, w, _ = pred.shape
+            if p not in names:  # (its mask count is the one fn2_photometric_masks fills through the table of all scales)
+                small.append(photometric.level(pred, self.imgs[p], self.masks[p], self.counts[i:i + 1], g, self.scales[p],
+                                               wgt))
+                continue
+            self.grey[p], self.warp[p], self.valid[p] = self._new(n, h, w), self._new(3, n, h, w), self._new(n, h, w)
+            self.coef[p] = self._new(2, n, h, w)
+            big.append(census.level(pred, self.imgs[p], self.masks[p], g, self.grey[p], self.warp[p], self.valid[p],
+                                    self.coef[p], self.census_counts[len(big):len(big) + 1], self.scales[p], wgt))
+        self.census_names = names
+        self.census_table = census.level_table(big) if big else None
+        self.small_table = photometric.level_table(small) if small else None
+        self.zeroed = [self.counts, self.census_counts]
+
+    def launch(self, s):
+        tr, lib = self.tr, self.tr.lib
+        self._frames_and_masks(s)
+        if self.census_table is not None:
+            nl = len(self.census_table)
+            _hip.check(lib.fn2_census_warp(self.census_table, nl, tr.N, s))
+            _hip.check(lib.fn2_census_cost(self.census_table, nl, tr.N, tr.photometric_q, _hip.ptr(tr.loss_dev), s))
+            _hip.check(lib.fn2_census_grad(self.census_table, nl, tr.N, tr.loss_scale, s))
+        if self.small_table is not None:
+            self._photometric(self.small_table, s)
+        self._smoothness(s)
 
 
 class Sparse(_Stage):
@@ -169,7 +222,7 @@ class Sparse(_Stage):
 def stage_for(trainer, with_edge_map=False):
     """The stage of the trainer's mode (its constructor has refused the combinations)."""
     if trainer.unsupervised:
-        return Photometric(trainer)
+        return Census(trainer) if trainer.data_term == "census" else Photometric(trainer)
     if trainer.sparse_gt:
         return Sparse(trainer)
     if trainer.hfem == "hard":

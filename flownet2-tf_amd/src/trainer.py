@@ -68,7 +68,7 @@ class FlowNetSTrainer:
                  add_hard_flow_mining="", lambda_weight=2.0, hard_examples_perc=50, optimizer="adam", momentum=None,
                  min_momentum=0.85, max_momentum=0.95, weight_decay=None, clip_grad_norm=-1.0, unsupervised=False,
                  photometric_q=0.4, occ_alpha=0.01, occ_beta=0.5, smoothness_weight=0.0, smoothness_order=1,
-                 edge_lambda=150.0, smoothness_eps=1e-3, sparse_gt=False):
+                 edge_lambda=150.0, smoothness_eps=1e-3, sparse_gt=False, data_term="photometric"):
         """dtype 'f32': everything on the fp32 matrix cores.  'f16x2': activations, activation gradients and the
         weight copies the convolutions read are split fp16 (3 fp16 MFMAs per product, fp32 accumulate); the master
         weights, their gradients and the Adam state stay fp32.
@@ -93,7 +93,14 @@ class FlowNetSTrainer:
         carries no label.  The labels stay the five NaN-aware downsamples; the loss behind them is src/sparse_epe.py's --
         every scale normalised by its own count of valid label pixels, gradient exactly 0 where there is none -- in two
         launches for all scales.  FlowNetS, FlowNetSD, FlowNetC and the last network of FlowNetCS / FlowNetCSS.  False
-        (default): the step launches what it launches without the argument."""
+        (default): the step launches what it launches without the argument.
+
+        data_term (unsupervised only): 'photometric' (default) is the loss above.  'census' replaces it by the ternary
+        census term of src/census.py at every scale that holds a 7 x 7 patch -- the soft Hamming distance between the
+        census descriptors of a frame's grey values and of its partner's warped ones, under the same robust function,
+        exponent and occlusion masks; it needs no brightness constancy.  Smaller scales keep the photometric term."""
+        from .census import check_data_term
+        self.data_term = check_data_term(data_term, unsupervised)  # before anything else is built
         self.sparse_gt = bool(sparse_gt)
         if self.sparse_gt:  # before anything else is built
             if unsupervised:
@@ -706,6 +713,7 @@ class FlowNetSTrainer:
 
     # the loss state by the names its readers know: that kind's stage or None, the latest labels, the captured mode
     _photo = property(lambda self: next((st for st in self._stages.values() if st.kind == "photometric"), None))
+    _census = property(lambda self: next((st for st in self._stages.values() if st.kind == "census"), None))
     _sparse = property(lambda self: next((st for st in self._stages.values() if st.kind == "sparse"), None))
     _labels = property(lambda self: self._stage.labels)
     _mining = property(lambda self: self._captured.kind if self._captured.kind in ("hard", "edges") else None)

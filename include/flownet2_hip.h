@@ -703,6 +703,59 @@ int fn2_smoothness_loss_grad(const fn2_photometric_level* levels, int n_levels, 
                              float eps, float smooth_weight, float grad_mult, int accumulate, float* loss_accum,
                              void* stream);
 
+/* ---------------------------------------------------------------- ternary census data term (unsupervised training)
+ * An ADDITION to the reference: the data term UnFlow, DDFlow and SelFlow train their final stages on, for pairs whose
+ * exposure changes between the frames.  The slot layout, s_l, f = scaled_flow(pred, s_l), X, Y, tf_taps, valid and the mask
+ * m = valid & ~occ are those of the photometric loss above.  Per level (h x w) and slot j, with R = 3 fixed at compile time:
+ *   Grey value.   G(p) = ((r + g) + b) * 85.0f, each operation rounded on its own (contraction off).  85 = 255 / 3: the
+ *                 constants below are UnFlow's and are tuned for a 0..255 range.  The plain channel mean is a decision:
+ *                 the loader's channel order is not fixed and the `pair` augmentation permutes channels.
+ *   Warped grey.  W(p) = tf_blend(taps(p), G[j^1] at the four taps); the kernel forms the partner's grey values on the
+ *                 fly from RGB with the same formula (they equal the stored G).
+ *                 DX(p) = (y1-Y)(Gc-Ga) + (Y-y0)(Gd-Gb), DY(p) = (x1-X)(Gb-Ga) + (X-x0)(Gd-Gc) on the clamped taps.
+ *                 V(p) = 1 if 0 <= X < w-1 and 0 <= Y < h-1 (NaN fails), else 0.  Where V = 0, W, DX and DY are stored
+ *                 as 0: nothing reads them there, and every buffer stays finite whatever pred holds.
+ *   Interior.     Omega = {R <= x < w-R, R <= y < h-R} (UnFlow's transform_mask): no patch leaves the level.
+ *   Distance.     For q in Omega and d in [-3,3]^2:  n(t) = t / sqrt(0.81 + t^2),  a = n(G(q+d) - G(q)),
+ *                 b = n(W(q+d) - W(q)),  e = (a-b)^2,  S(q) = sum_d V(q+d) * e / (0.1 + e);  S = 0 outside Omega.
+ *                 The factor V(q+d) is an ADDITION of the kind `valid` is: where V = 0 tf_warp returns 0 or
+ *                 extrapolates, such a value enters nobody's descriptor and the pixel gets no gradient from it.
+ *                 Occluded neighbours stay in: their W is a real sample.
+ *   Mask, count.  mc(q) = mask(q) * V(q) * [q in Omega],  Mc = sum mc (an integer below 2^24 kept as float).
+ *   Loss.         L = weight * sum mc * psi(S) / (2 Mc + 1e-6),  psi(S) = (S + 0.01)^q (accurate powf): abs_robust_loss in
+ *                 its loss_mean form (src/utils.py:378-395) on the distance.  The coefficient is formed in double.
+ *                 A level with min(h, w) < 7 has Mc = 0, loss 0 and gradient exactly 0.
+ *   Gradient.     The masks, V, Mc and G are constants.  c(q) = mc(q) * q_exp * psi(S) / (S + 0.01),
+ *                 k(q,d) = V(q+d) * (-2 (a-b) * 0.1 / (0.1 + e)^2) * 0.81 / (0.81 + tb^2)^1.5,  tb = W(q+d) - W(q),
+ *                 dW(p) = sum_{d : p-d in Omega} c(p-d) k(p-d, d) - [p in Omega] c(p) sum_d k(p, d),
+ *                 dpred(p) = grad_mult * weight * s_l / (2 Mc + 1e-6) * dW(p) * (DX(p), DY(p)).
+ *                 A gather with plain stores: deterministic.  The gradient is 0 wherever V = 0.
+ * `levels` is a HOST array of 1..8 entries (no null pointer, h, w >= 1, h * w <= 2^30, pred / dpred 8-byte aligned, the
+ * other buffers 4-byte aligned, n even); it travels to the kernel by value and all levels run in ONE launch.  No allocation,
+ * no host synchronisation.  No address depends on data. */
+typedef struct {
+  const float* pred; /* [n,h,w,2] fp32, dense */
+  const float* img;  /* [n,h,w,3] the frames at this level's size */
+  const float* mask; /* [n,h,w]   0 / 1: fn2_photometric_masks' output, or all ones */
+  float* dpred;      /* [n,h,w,2] stored by fn2_census_grad, every pixel */
+  float* grey;       /* [n,h,w]   G, written by fn2_census_warp */
+  float* warp;       /* [3,n,h,w] the planes W, DX, DY, written by fn2_census_warp */
+  float* valid;      /* [n,h,w]   V as 0 / 1, written by fn2_census_warp */
+  float* coef;       /* [2,n,h,w] the planes S and c, written by fn2_census_cost */
+  float* count;      /* one float: fn2_census_warp ADDS Mc into it (the caller zeroes it) */
+  int32_t h, w;
+  float scale;       /* prediction -> pixels of this level */
+  float weight;
+} fn2_census_level;
+/* G, W, DX, DY, V of every level, and count += Mc. */
+int fn2_census_warp(const fn2_census_level* levels, int n_levels, int n, void* stream);
+/* S and c of every level from LDS tiles of G, W, V with a 3-pixel halo; loss_accum += sum over the levels of L (one atomic
+ * per block and level); 0 < q <= 1.  Reads what fn2_census_warp wrote, count included. */
+int fn2_census_cost(const fn2_census_level* levels, int n_levels, int n, float q, float* loss_accum, void* stream);
+/* dpred of every pixel of every level (zeros included) from LDS tiles of G, W, V, c with the halo; grad_mult as in
+ * fn2_epe_loss_grad. */
+int fn2_census_grad(const fn2_census_level* levels, int n_levels, int n, float grad_mult, void* stream);
+
 /* ---------------------------------------------------------------- multi-scale EPE over sparse ground truth (KITTI)
  * The supervised loss for ground truth that does not cover the frame (KITTI, HD1K, Middlebury).  A label pixel whose u or
  * v is not finite carries no ground truth: that is what the reference's Downsample op (fn2_downsample_f32 /
