@@ -25,6 +25,19 @@ __device__ __forceinline__ void warp3(const float* __restrict__ img, long nb, in
   o[2] = cTL * tl.b + cTR * tr.b + cBL * bl.b + cBR * br.b;
 }
 
+// ChannelNorm of a flow vector (flownet2.py:25-31).  The squares of a finite vector overflow fp32 beyond |v| ~ 1.8e19
+// although its norm is representable: only then is it taken again on the vector scaled by 2^-70 (exact), so every
+// other input -- NaN and infinite flows included -- gives the bits of the plain expression.
+__device__ __forceinline__ float norm2(float x, float y) {
+  float r = sqrtf(x * x + y * y);
+  if (r == INFINITY && fabsf(x) < INFINITY && fabsf(y) < INFINITY) {
+    x *= 0x1p-70f;
+    y *= 0x1p-70f;
+    r = sqrtf(x * x + y * y) * 0x1p70f;
+  }
+  return r;
+}
+
 // A full-resolution flow field given either as itself (ph == 0: `p` is [N,H,W,2]) or as the quarter-resolution
 // predict_flow2 it is resized from (`flow = resize_bilinear(scale * predict_flow2)`, align_corners, flownet_s.py:105-109):
 // then the consumer interpolates its pixel itself -- resize_bilinear_c2_kernel's arithmetic, operation for operation --
@@ -33,16 +46,12 @@ struct FlowSrc { const float* p; int ph, pw; float sy, sx, scale; float* keep; }
 
 __device__ __forceinline__ float2 flow_at(const FlowSrc& f, int n, int y, int x, long pix) {
   if (f.ph == 0) return *reinterpret_cast<const float2*>(f.p + pix * 2);
-  const float fy = (float)y * f.sy;
-  const int y0 = (int)floorf(fy);
-  const int y1 = min(y0 + 1, f.ph - 1);
-  const float ly = fy - (float)y0;
+  int y0, y1, x0, x1;
+  float ly, lx;
+  resize_coord(y, f.sy, f.ph, y0, y1, ly);
+  resize_coord(x, f.sx, f.pw, x0, x1, lx);
   const float2* r0 = reinterpret_cast<const float2*>(f.p) + ((long)n * f.ph + y0) * f.pw;
   const float2* r1 = reinterpret_cast<const float2*>(f.p) + ((long)n * f.ph + y1) * f.pw;
-  const float fx = (float)x * f.sx;
-  const int x0 = (int)floorf(fx);
-  const int x1 = min(x0 + 1, f.pw - 1);
-  const float lx = fx - (float)x0;
   float2 r = bilerp_c2(r0[x0], r0[x1], r1[x0], r1[x1], lx, ly, f.scale);
   // the vector is used as the resize launch would have STORED it: without this the final multiply by `scale` contracts
   // with the consumer's first addition (x + u in the warp) and the results differ in the last bit
@@ -75,8 +84,13 @@ __global__ void __launch_bounds__(256) stack_input_kernel(const float* __restric
       const float d = av - wv[c];
       e += d * d;
     }
-    v[9] = f.x * 0.05f;   // flownet_cs.py:34
-    v[10] = f.y * 0.05f;
+    {
+      // the ROUNDED fp32 product in every storage format: left contractable, the split-fp16 store's `v - hi` fused with
+      // this multiply (in channel 9 only) and its lo part came from the unrounded product, not from the value f32 stores
+#pragma clang fp contract(off)
+      v[9] = f.x * 0.05f;   // flownet_cs.py:34
+      v[10] = f.y * 0.05f;
+    }
     v[11] = sqrtf(e);     // brightness error, flownet_cs.py:24-27
     v[12] = v[13] = v[14] = v[15] = 0.f;
     const size_t opix = ((size_t)(pix / W / H) * (H + 2 * pad) + y + pad) * (W + 2 * pad) + x + pad;
@@ -110,8 +124,8 @@ __global__ void __launch_bounds__(256) fusion_input_kernel(const float* __restri
       ecs += d2 * d2;
     }
     v[3] = sd.x; v[4] = sd.y; v[5] = cs.x; v[6] = cs.y;           // flownet2.py:41-43
-    v[7] = sqrtf(sd.x * sd.x + sd.y * sd.y);                       // ChannelNorm(flow_sd), :30
-    v[8] = sqrtf(cs.x * cs.x + cs.y * cs.y);                       // ChannelNorm(flow_css), :31
+    v[7] = norm2(sd.x, sd.y);                                      // ChannelNorm(flow_sd), :30
+    v[8] = norm2(cs.x, cs.y);                                      // ChannelNorm(flow_css), :31
     v[9] = sqrtf(esd);                                             // :35
     v[10] = sqrtf(ecs);                                            // :39
     v[11] = v[12] = v[13] = v[14] = v[15] = 0.f;
@@ -127,12 +141,22 @@ static inline int grid_for(long work_items, int block) {
   return (int)g;
 }
 
-static int check_out16(const fn2_tensor* out, int c, const char* what) {
+static int check_out16(const fn2_tensor* out, int c, int pad, const char* what) {
   FN2_REQUIRE(out && out->data, "%s: null output", what);
-  FN2_REQUIRE(out->c == c, "%s: output view must have %d channels", what, c);
-  FN2_REQUIRE(out->cs % 8 == 0 && out->c0 % 8 == 0 && out->c0 + 16 <= out->cs,
+  FN2_REQUIRE(out->n >= 1 && out->c == c, "%s: output view must have %d channels and n >= 1", what, c);
+  FN2_REQUIRE(out->c0 >= 0 && out->cs % 8 == 0 && out->c0 % 8 == 0 && out->c0 + 16 <= out->cs,
               "%s: output needs a 16-channel, 8-aligned slot", what);
   FN2_REQUIRE(out->dtype >= FN2_F32 && out->dtype <= FN2_F16X2, "%s: bad dtype", what);
+  FN2_REQUIRE(pad >= 0 && out->h > 2 * pad && out->w > 2 * pad, "%s: bad border", what);
+  FN2_REQUIRE(((size_t)out->data & 15) == 0, "%s: output must be 16-byte aligned", what);  // the 16-byte group stores
+  return FN2_OK;
+}
+
+// the 12-byte rgb loads need 4-byte alignment, the float2 flow loads and stores 8-byte (a null flow_out passes)
+static int check_in_align(const float* a, const float* b, const float* f0, const float* f1, const float* f2, const float* f3,
+                          const char* what) {
+  FN2_REQUIRE((((size_t)a | (size_t)b) & 3) == 0, "%s: images must be 4-byte aligned", what);
+  FN2_REQUIRE((((size_t)f0 | (size_t)f1 | (size_t)f2 | (size_t)f3) & 7) == 0, "%s: flows must be 8-byte aligned", what);
   return FN2_OK;
 }
 
@@ -288,18 +312,20 @@ static int stack_input_launch(const float* a, const float* b, const FlowSrc& f, 
 
 int fn2_stack_input(const float* a, const float* b, const float* flow, const fn2_tensor* out, int pad, void* stream) {
   FN2_REQUIRE(a && b && flow, "stack_input: null pointer");
-  int rc = check_out16(out, 12, "stack_input");
+  int rc = check_out16(out, 12, pad, "stack_input");
   if (rc) return rc;
-  FN2_REQUIRE(pad >= 0 && out->h > 2 * pad && out->w > 2 * pad, "bad border");
+  rc = check_in_align(a, b, flow, nullptr, nullptr, nullptr, "stack_input");
+  if (rc) return rc;
   return stack_input_launch(a, b, flow_src(flow, 0, 0, 1.f, nullptr, 0, 0), out, pad, stream);
 }
 
 int fn2_stack_input_pf(const float* a, const float* b, const float* pf, int pf_h, int pf_w, float scale, float* flow_out,
                        const fn2_tensor* out, int pad, void* stream) {
   FN2_REQUIRE(a && b && pf && pf_h >= 1 && pf_w >= 1, "stack_input_pf: null pointer / bad size");
-  int rc = check_out16(out, 12, "stack_input_pf");
+  int rc = check_out16(out, 12, pad, "stack_input_pf");
   if (rc) return rc;
-  FN2_REQUIRE(pad >= 0 && out->h > 2 * pad && out->w > 2 * pad, "bad border");
+  rc = check_in_align(a, b, pf, flow_out, nullptr, nullptr, "stack_input_pf");
+  if (rc) return rc;
   return stack_input_launch(a, b, flow_src(pf, pf_h, pf_w, scale, flow_out, out->h - 2 * pad, out->w - 2 * pad), out, pad, stream);
 }
 
@@ -325,9 +351,10 @@ static int fusion_input_launch(const float* a, const float* b, const FlowSrc& fs
 int fn2_fusion_input(const float* a, const float* b, const float* flow_sd, const float* flow_css,
                      const fn2_tensor* out, int pad, void* stream) {
   FN2_REQUIRE(a && b && flow_sd && flow_css, "fusion_input: null pointer");
-  int rc = check_out16(out, 11, "fusion_input");
+  int rc = check_out16(out, 11, pad, "fusion_input");
   if (rc) return rc;
-  FN2_REQUIRE(pad >= 0 && out->h > 2 * pad && out->w > 2 * pad, "bad border");
+  rc = check_in_align(a, b, flow_sd, flow_css, nullptr, nullptr, "fusion_input");
+  if (rc) return rc;
   return fusion_input_launch(a, b, flow_src(flow_sd, 0, 0, 1.f, nullptr, 0, 0), flow_src(flow_css, 0, 0, 1.f, nullptr, 0, 0),
                              out, pad, stream);
 }
@@ -336,9 +363,10 @@ int fn2_fusion_input_pf(const float* a, const float* b, const float* pf_sd, floa
                         const float* pf_css, float scale_css, float* flow_css_out, int pf_h, int pf_w,
                         const fn2_tensor* out, int pad, void* stream) {
   FN2_REQUIRE(a && b && pf_sd && pf_css && pf_h >= 1 && pf_w >= 1, "fusion_input_pf: null pointer / bad size");
-  int rc = check_out16(out, 11, "fusion_input_pf");
+  int rc = check_out16(out, 11, pad, "fusion_input_pf");
   if (rc) return rc;
-  FN2_REQUIRE(pad >= 0 && out->h > 2 * pad && out->w > 2 * pad, "bad border");
+  rc = check_in_align(a, b, pf_sd, pf_css, flow_sd_out, flow_css_out, "fusion_input_pf");
+  if (rc) return rc;
   const int oh = out->h - 2 * pad, ow = out->w - 2 * pad;
   return fusion_input_launch(a, b, flow_src(pf_sd, pf_h, pf_w, scale_sd, flow_sd_out, oh, ow),
                              flow_src(pf_css, pf_h, pf_w, scale_css, flow_css_out, oh, ow), out, pad, stream);

@@ -80,6 +80,19 @@ __device__ __forceinline__ void split8(const float* v, uint4& hi, uint4& lo) {
   hi = __builtin_bit_cast(uint4, h);
   lo = __builtin_bit_cast(uint4, l);
 }
+// Source coordinate of output index i on one axis of tf.image.resize_bilinear(align_corners=True): f = float(i) * s ROUNDED
+// to fp32, lo = floor(f), hi = min(lo + 1, n_in - 1), frac = f - lo (exact).  Contraction is off: fused into one
+// fma(i, s, -lo) the fraction comes from the unrounded product -- another coordinate than the one floor() saw, by up to
+// half an ulp of f, which times the slope of the input was 4.5x the arithmetic rounding at 128 -> 512 columns -- and
+// whether that happened was the compiler's choice per kernel.  Shared by the resize kernels (ops.hip) and flow_at (elem.hip).
+__device__ __forceinline__ void resize_coord(int i, float s, int n_in, int& lo, int& hi, float& frac) {
+#pragma clang fp contract(off)
+  const float f = (float)i * s;
+  lo = (int)floorf(f);
+  hi = min(lo + 1, n_in - 1);
+  frac = f - (float)lo;
+}
+
 // One two-channel pixel of tf.image.resize_bilinear(align_corners=True) times `scale` from its four neighbours.  Shared by
 // the resize kernel (ops.hip) and the ops that interpolate their own flow vector (elem.hip: flow_at), so that
 // both produce the same bits whatever the surrounding code is.

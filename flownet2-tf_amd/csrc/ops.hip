@@ -527,10 +527,10 @@ __global__ void __launch_bounds__(256) resize_bilinear_kernel(const float* __res
     const int x = (int)(o % ow);
     const int y = (int)((o / ow) % oh);
     const int n = (int)(o / ow / oh);
-    const float fy = (float)y * sy, fx = (float)x * sx;
-    const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
-    const int y1 = min(y0 + 1, Hin - 1), x1 = min(x0 + 1, Win - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    int y0, y1, x0, x1;
+    float ly, lx;
+    resize_coord(y, sy, Hin, y0, y1, ly);
+    resize_coord(x, sx, Win, x0, x1, lx);
     const float* b = in + (long)n * Hin * Win * C;
     for (int c = 0; c < C; ++c) {
       const float tl = b[((long)y0 * Win + x0) * C + c], tr = b[((long)y0 * Win + x1) * C + c];
@@ -550,19 +550,17 @@ __global__ void __launch_bounds__(256) resize_bilinear_c2_kernel(const float* __
   const int y = blockIdx.y % oh, n = blockIdx.y / oh;
   const int xp = blockIdx.x * 256 + threadIdx.x;
   if (2 * xp >= ow) return;
-  const float fy = (float)y * sy;
-  const int y0 = (int)floorf(fy);
-  const int y1 = min(y0 + 1, Hin - 1);
-  const float ly = fy - (float)y0;
+  int y0, y1;
+  float ly;
+  resize_coord(y, sy, Hin, y0, y1, ly);
   const float2* r0 = reinterpret_cast<const float2*>(in) + ((long)n * Hin + y0) * Win;
   const float2* r1 = reinterpret_cast<const float2*>(in) + ((long)n * Hin + y1) * Win;
   float res[4];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const float fx = (float)(2 * xp + j) * sx;
-    const int x0 = (int)floorf(fx);
-    const int x1 = min(x0 + 1, Win - 1);
-    const float lx = fx - (float)x0;
+    int x0, x1;
+    float lx;
+    resize_coord(2 * xp + j, sx, Win, x0, x1, lx);
     const float2 r = bilerp_c2(r0[x0], r0[x1], r1[x0], r1[x1], lx, ly, scale);
     res[2 * j] = r.x;
     res[2 * j + 1] = r.y;

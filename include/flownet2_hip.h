@@ -356,7 +356,10 @@ int fn2_correlation_fused_kernel_name(const fn2_tensor* a, const fn2_tensor* b, 
                                       int max_displacement, int stride_2, char* name, int cap);
 
 /* Stacked-net input (flownet_cs.py:21-36): out view (16-channel padded) =
- * [a(3) | b(3) | warp(b, flow)(3) | flow*0.05(2) | sqrt(sum_c (a-warp)^2)(1) | 0...]. */
+ * [a(3) | b(3) | warp(b, flow)(3) | flow*0.05(2) | sqrt(sum_c (a-warp)^2)(1) | 0...].
+ * This op, fn2_fusion_input and their _pf forms refuse (FN2_ERR_INVALID_ARGUMENT) a view with n < 1, no interior inside
+ * the border, a slot that is not 16 channels at a multiple of 8, out->data that is not 16-byte aligned, images that are
+ * not 4-byte aligned and flow / predict_flow2 / flow_out pointers that are not 8-byte aligned. */
 int fn2_stack_input(const float* a, const float* b, const float* flow, const fn2_tensor* out, int pad,
                     void* stream);
 
